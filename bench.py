@@ -10,8 +10,14 @@ and the posterior draw, all stages.  value = denoising-steps/s = (images x sum_s
 over all ranks (weak scaling: the per-GPU batch is fixed, every rank samples its own rows, one RCCL
 all_gather of the finished images inside the timed region).
 
-Also printed in the same JSON line:
+A plain run sets up, warms up, times the --steps steps and prints the JSON line (headline value and ms_per_step).
+--dump-outputs DIR also writes the images the last timed step returned to DIR/images.npy (float32; inputs are seeded, so
+two builds run with the same arguments can be compared output for output).
+
+With --full the same JSON line also carries what the headline does not need:
+  pipelined_equals_synchronous, value_no_pipeline, value_one_lane   the pipelined mode checked and timed against synchronous calls
   roofline      the dominant kernel launch of the dominant stage, timed live with HIP events on the launch stream
+  t5_encode, secondary   the T5 leg and the other BASELINE configurations, each in a run of its own
   cpu_baseline  the oracle (a CPU port of the reference's algorithm) timed on this host's cores on a bounded sample
 """
 import argparse
@@ -31,6 +37,22 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_F32_PEAK_TFLOPS = 157.3  # v_mfma_f32_16x16x4_f32, dense
 MFMA_F16_PEAK_TFLOPS = 2500.0 # dense f16/bf16 MFMA peak (MI355X_MICROARCH.md; the sparsity figure is not used)
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, images):
+    """--dump-outputs: the images one sample() call returned, as DIR/images.npy in float32.  Where all rows would exceed
+    DUMP_LIMIT_BYTES, a fixed seeded subset of whole images (rows kept in ascending order) -- the same rows for the same arguments."""
+    import numpy as np
+    images = images.detach().float().cpu()
+    per_row = images[0].numel() * 4
+    keep = min(images.shape[0], DUMP_LIMIT_BYTES // per_row)
+    if keep < images.shape[0]:
+        rows = torch.randperm(images.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        print(f"bench: --dump-outputs keeps images {rows.tolist()} of {images.shape[0]} ({DUMP_LIMIT_BYTES >> 20} MB limit)", file=sys.stderr)
+        images = images[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "images.npy"), images.numpy())
 
 
 def synthetic_text(batch, length=64, dim=512, seed=7, row0=0):
@@ -371,7 +393,7 @@ def secondary_lines(timesteps, cond_scale):
                                                ("config5_cascade64_256_1024_B8_half", "cascade64_256_1024", 8, "half", 3)):
         cmd = [sys.executable, os.path.abspath(__file__), "--workload", workload, "--batch", str(B), "--precision", precision, "--steps", str(calls),
                "--warmup", "3" if calls > 3 else "1", "--timesteps", str(timesteps), "--cond-scale", str(cond_scale),
-               "--no-secondary", "--no-cpu-baseline", "--no-t5", "--no-live-pmc"] + ([] if workload == "cascade64_256_1024" else ["--no-breakdown"])      # (the secondary legs keep the committed-profile look-up: bounded run time)
+               "--full", "--no-secondary", "--no-cpu-baseline", "--no-t5", "--no-live-pmc"] + ([] if workload == "cascade64_256_1024" else ["--no-breakdown"])      # (the secondary legs keep the committed-profile look-up: bounded run time)
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
         r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -548,7 +570,13 @@ def main():
     ap.add_argument("--breakdown-out", default="")
     ap.add_argument("--lanes", type=int, default=0, help="independent call lanes of the pipelined mode (sets of stage streams / workspaces / graphs that "
                     "sample(_async=True) alternates between; 0 = the library default MINIMAGEN_SAMPLE_LANES = 2, 1 = one lane: only the stages of successive calls overlap)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline: the pipelined-vs-synchronous check and timings, "
+                    "the per-launch breakdown / roofline, the T5 leg, the secondary configurations and the CPU baseline (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the images the last timed step returned to DIR/images.npy "
+                    f"(float32; a fixed, seeded subset of the images when all of them would exceed {DUMP_LIMIT_BYTES >> 20} MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if pmc_child_mode:
         return pmc_child(args)
 
@@ -643,10 +671,10 @@ def main():
     pipelined = not args.no_pipeline
     for k in range(args.warmup):
         one_step(k, pipelined)
-    # the benched mode is value-checked outside the timed region: the second of two back-to-back pipelined calls (its base stage ran
-    # under the first call's super-resolution stage) against the same call made synchronously
+    # --full: the benched mode is value-checked outside the timed region: the second of two back-to-back pipelined calls (its base stage
+    # ran under the first call's super-resolution stage) against the same call made synchronously
     pipe_ok = None
-    if pipelined:
+    if pipelined and args.full:
         torch.cuda.synchronize()
         ref_out = one_step(7, False, gather=False).clone()
         torch.cuda.synchronize()
@@ -664,8 +692,10 @@ def main():
     dt, mine, out = timed(args.steps, pipelined)
     assert torch.isfinite(out).all() and out.shape[0] == gB
     im.check_device_status()            # no kernel with inter-workgroup waits (the grouped sampler tail) gave up waiting
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     dt_sync = dt_one = None
-    if pipelined:                       # the reference's sample() is synchronous: report that mode beside the pipelined headline
+    if pipelined and args.full:         # the reference's sample() is synchronous: report that mode beside the pipelined headline
         dt_sync, _, _ = timed(max(2, min(args.steps, 8)), False)
         dt_sync /= max(2, min(args.steps, 8))
         if MI.SAMPLE_LANES > 1:         # ... and the pipelined mode with ONE lane (stage overlap of successive calls only)
@@ -680,7 +710,7 @@ def main():
     if dist_on:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, {"rank": rank, "rows": B, "seconds": mine})
-        if not one_gpu:                 # the collective alone, on its stream, with HIP events
+        if not one_gpu and args.full:   # the collective alone, on its stream, with HIP events
             loc = torch.zeros(B, 3, sizes[-1], sizes[-1], device=dev)
             with torch.cuda.stream(gstream):
                 gather_samples(loc, gB)
@@ -708,17 +738,18 @@ def main():
                    "timesteps": args.timesteps, "parallelism": f"dp{world}",
                    "call_mode": (f"successive sample() calls PIPELINED (_async=True) over {MI.SAMPLE_LANES} call lane(s) of per-stage HIP streams: "
                                  "two calls are in flight side by side and the base stage of a call runs under the super-resolution stage of the one "
-                                 "before it; outputs bit-identical to synchronous calls, checked in this run; value_one_lane = stage overlap of "
+                                 "before it; outputs bit-identical to synchronous calls, checked in a --full run; value_one_lane = stage overlap of "
                                  "successive calls only (round 2's mode), value_no_pipeline = the same calls one at a time, the reference's synchronous semantics") if pipelined
                                 else "synchronous sample() calls, one at a time (the reference's semantics)"},
         "images_per_s": gB * args.steps / dt,
         "pipelined": pipelined,
     }
     if pipelined:
+        res["lanes"] = MI.SAMPLE_LANES
+    if pipelined and args.full:
         res["pipelined_equals_synchronous"] = pipe_ok
         res["value_no_pipeline"] = gB * steps_per_sample / dt_sync
         res["ms_per_step_no_pipeline"] = dt_sync * 1e3
-        res["lanes"] = MI.SAMPLE_LANES
         if dt_one is not None:
             res["value_one_lane"] = gB * steps_per_sample / dt_one
             res["ms_per_step_one_lane"] = dt_one * 1e3
@@ -726,7 +757,7 @@ def main():
         res["per_rank"] = [dict(r, denoising_steps_per_s=r["rows"] * steps_per_sample * args.steps / r["seconds"]) for r in per_rank]
         res["all_gather_ms"] = gather_ms
 
-    if rank == 0 and not args.no_breakdown:
+    if rank == 0 and args.full and not args.no_breakdown:
         stage = n_stages - 1
         rows = op_breakdown(im, stage, B, args.cond_scale, precision=args.precision)
         total_ms = sum(r["ms"] for r in rows)
@@ -794,9 +825,9 @@ def main():
         if args.breakdown_out:
             with open(args.breakdown_out, "w") as f:
                 json.dump(rows, f, indent=1)
-    if rank == 0 and not args.no_t5:
+    if rank == 0 and args.full and not args.no_t5:
         res["t5_encode"] = t5_leg(dev, B)
-    if rank == 0 and world == 1 and not args.no_secondary and args.workload == "cascade64_256" and args.precision == "fp32":
+    if rank == 0 and world == 1 and args.full and not args.no_secondary and args.workload == "cascade64_256" and args.precision == "fp32":
         res["secondary"] = secondary_lines(args.timesteps, args.cond_scale)
         res["secondary"]["train_step_sr_unet_B32"] = train_step_leg()
         res["secondary"]["wide_unet_default_B16"] = wide_step_leg()
@@ -805,7 +836,7 @@ def main():
             res["roofline"]["wide_unet_default_step_ms"] = wide.get("ms_per_denoising_step")
             res["roofline"]["wide_unet_default_mfma_frac"] = wide["roofline"]["frac"]
             res["roofline"]["wide_unet_default_mfma_issued_frac"] = wide["roofline"]["issued_frac"]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(res))

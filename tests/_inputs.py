@@ -21,6 +21,11 @@ def seeded(shape, seed):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
 
 
+def fingerprint(sd):
+    """name -> (shape, float64 sum) of every tensor of a state dict: recorded with golden outputs computed from seeded weights"""
+    return {k: (tuple(v.shape), float(v.double().sum())) for k, v in sd.items()}
+
+
 def text(meta):
     emb, mask = R.synthetic_text(2, length=meta["L"], seed=meta["text_seed"])
     r, c = 1, 6

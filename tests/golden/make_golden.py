@@ -1,7 +1,8 @@
 """Generate the golden fixtures in tests/golden/ by running the UNMODIFIED reference
 (/root/reference, through oracle/ref_loader.py) on CPU.  Build-container only.
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py                      # everything
+    python tests/golden/make_golden.py reference_direct     # reference_direct.pt / reference_train_unet{1,2}.pt only
 
 Inputs are regenerated from the recorded seeds by tests (torch CPU generators are
 deterministic for a given torch build; the GPU box runs the same image), so only
@@ -131,5 +132,74 @@ def main():
         print(f, os.path.getsize(os.path.join(HERE, f)))
 
 
+def reference_direct():
+    """reference_direct.pt / reference_train_unet{1,2}.pt: what the unmodified reference computes on the inputs of the tests that compare against it
+    (tests/test_oracle.py, test_host.py, test_training.py), so that those tests need no reference tree.  Weights other than the golden
+    state dicts are the package's own seeded initialisation loaded into the reference modules; their fingerprint is recorded with them."""
+    from minimagen_amd.Imagen import Imagen
+    from minimagen_amd.Unet import Unet
+    from tests._inputs import fingerprint
+    from tests.test_training import BASE, SR
+    from tests.test_unet import SWEEP
+
+    def ref_unet(seed, **kw):
+        torch.manual_seed(seed)
+        sd = Unet(**kw).state_dict()
+        ru = ref.Unet(**kw)
+        ru.load_state_dict(sd, strict=True)
+        return ru.eval(), fingerprint(sd)
+
+    sd0 = torch.load(os.path.join(HERE, "unet0_sd.pt"), weights_only=False)
+    p = json.load(open(os.path.join(HERE, "unet_params.json")))
+    out = {}
+    with torch.no_grad():
+        u0 = ref.Unet(**p["unet0"])
+        u0.load_state_dict(sd0)
+        emb, mask = R.synthetic_text(3, length=40, seed=3)
+        out["base_cs3"] = u0.eval().forward_with_cond_scale(seeded((3, 3, 64, 64), 5), torch.tensor([0, 24, 7]), text_embeds=emb, text_mask=mask,
+                                                            cond_scale=3.)
+        ua, fp = ref_unet(3, dim=16, dim_mults=(1, 2), num_resnet_blocks=1, layer_attns=(False, True), layer_cross_attns=(False, True),
+                          attend_at_middle=True, memory_efficient=False)
+        out["attn"] = dict(fingerprint=fp, out=ua(seeded((2, 3, 32, 32), 6), torch.tensor([3, 9]), text_embeds=emb[:2], text_mask=mask[:2]))
+        out["sweep"] = {}
+        for case, (kw, S, extra) in sorted(SWEEP.items()):
+            ru, fp = ref_unet(1, **kw)
+            E, ch = extra.get("E", 512), extra.get("ch", 3)
+            emb, mask = R.synthetic_text(2, length=10, seed=3)
+            if E != 512:
+                emb = torch.randn(2, 10, E, generator=torch.Generator().manual_seed(3)).masked_fill(~mask[:, :, None], 0.)
+            kwargs = dict(text_embeds=emb, text_mask=None if extra.get("nomask") else mask)
+            if extra.get("lowres"):
+                kwargs.update(lowres_cond_img=seeded((2, ch, S, S), 7), lowres_noise_times=torch.tensor([5, 5]))
+            out["sweep"][case] = dict(fingerprint=fp, out=ru(seeded((2, ch, S, S), 6), torch.tensor([3, 9]), **kwargs))
+        rgd = ref.diffusion_model.GaussianDiffusion(timesteps=100)
+        g = torch.Generator().manual_seed(3)
+        x0, eps = torch.randn(4, 3, 8, 8, generator=g), torch.randn(4, 3, 8, 8, generator=g)
+        t = torch.tensor([0, 1, 57, 99])
+        xt = rgd.q_sample(x0, t, eps)
+        out["diffusion"] = dict(xt=xt, x0_hat=rgd.predict_start_from_noise(xt, t, eps), q_posterior=tuple(rgd.q_posterior(x0, xt, t)))
+    torch.save(out, os.path.join(HERE, "reference_direct.pt"))
+
+    torch.manual_seed(7)
+    ours = Imagen((Unet(**BASE), Unet(**SR)), text_encoder_name="t5_small", image_sizes=(16, 32), timesteps=60)
+    theirs = ref.Imagen(unets=(ref.Unet(**BASE), ref.Unet(**SR)), text_encoder_name="t5_small", image_sizes=(16, 32), timesteps=60).train()
+    theirs.load_state_dict(ours.state_dict())
+    imgs = torch.rand(2, 3, 48, 48, generator=torch.Generator().manual_seed(8))
+    emb, mask = R.synthetic_text(2, length=11, seed=5)
+    for n in (1, 2):                           # one file per U-Net: each stays well under the size limit of a committed file
+        torch.manual_seed(11)
+        lb = theirs(imgs, text_embeds=emb, text_masks=mask, unet_number=n)
+        lb.backward()
+        torch.save(dict(fingerprint=fingerprint(ours.state_dict()), loss=float(lb.detach()),
+                        grads={name: prm.grad.clone() for name, prm in theirs.unets[n - 1].named_parameters()}),
+                   os.path.join(HERE, f"reference_train_unet{n}.pt"))
+    for f in ("reference_direct.pt", "reference_train_unet1.pt", "reference_train_unet2.pt"):
+        print(f, os.path.getsize(os.path.join(HERE, f)))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["reference_direct"]:
+        reference_direct()
+    else:
+        main()
+        reference_direct()

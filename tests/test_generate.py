@@ -92,7 +92,7 @@ def test_bench_two_ranks_control_flow_on_one_gpu(tmp_path):
     port = str(29000 + os.getpid() % 1500)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port,
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "2", "--timesteps", "25",
-           "--no-breakdown", "--no-cpu-baseline", "--no-secondary", "--no-t5"]
+           "--full", "--no-breakdown", "--no-cpu-baseline", "--no-secondary", "--no-t5"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -123,7 +123,7 @@ def test_bench_two_ranks_over_rccl():
     port = str(27000 + os.getpid() % 1500)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port,
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--timesteps", "25",
-           "--no-breakdown", "--no-cpu-baseline", "--no-secondary", "--no-t5"]
+           "--full", "--no-breakdown", "--no-cpu-baseline", "--no-secondary", "--no-t5"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -144,12 +144,35 @@ def test_bench_rccl_calls_with_a_group_of_one():
     port = str(25000 + os.getpid() % 1500)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", port,
            os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--timesteps", "25",
-           "--no-breakdown", "--no-cpu-baseline", "--no-secondary", "--no-t5"]
+           "--full", "--no-breakdown", "--no-cpu-baseline", "--no-secondary", "--no-t5"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["all_gather_ms"] > 0 and line["pipelined_equals_synchronous"]
     assert [r["rows"] for r in line["per_rank"]] == [2]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """a plain bench.py run (no --full): the headline keys and nothing of the --full legs; --dump-outputs holds the images of the last
+    timed step, and the same arguments give the same images"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MINIMAGEN_DIST_SINGLE", "MINIMAGEN_BENCH_ONE_GPU")}
+    dumps = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--timesteps", "25",
+               "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "denoising-steps/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert not {"pipelined_equals_synchronous", "value_no_pipeline", "roofline", "t5_encode", "secondary", "cpu_baseline"} & set(line)
+        dumps.append(np.load(tmp_path / run / "images.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (2, 3, 256, 256) and np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 _RCCL_ONE = r'''

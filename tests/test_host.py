@@ -195,6 +195,28 @@ def test_bench_contract_helpers():
     assert torch.equal(emb2, emb[26:30]) and torch.equal(mask2, mask[26:30])
     t = bench.pmc_traffic({"kernel": "cross_attn"}, 64, 256)
     assert t["traffic"] is None or 3e7 < t["traffic"] < 1e8
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
+    bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert bad.returncode != 0 and "--steps" in bad.stderr
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: all images as float32 when they fit the limit, otherwise the same seeded subset of whole images every time"""
+    import importlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    imgs = torch.randn(6, 3, 4, 4, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "all"), imgs)
+    got = np.load(tmp_path / "all" / "images.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, imgs.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 3 * 4 * 4 * 4)              # room for 4 of the 6 images
+    bench.dump_outputs(str(tmp_path / "a"), imgs)
+    bench.dump_outputs(str(tmp_path / "b"), imgs)
+    a, b = np.load(tmp_path / "a" / "images.npy"), np.load(tmp_path / "b" / "images.npy")
+    assert a.shape == (4, 3, 4, 4) and np.array_equal(a, b)
+    rows = [next(r for r in range(6) if np.array_equal(x, imgs[r].float().numpy())) for x in a]
+    assert rows == sorted(set(rows))
 
 
 def test_minimagen_import_path_is_the_amd_implementation():
@@ -218,8 +240,8 @@ def test_minimagen_import_path_is_the_amd_implementation():
 
 
 def test_gaussian_diffusion_public_methods():
-    """q_sample / q_posterior / predict_start_from_noise (diffusion_model.py:89-162) on the bit-identical tables: against the live
-    reference when it is present, always against the oracle's scalar forms"""
+    """q_sample / q_posterior / predict_start_from_noise (diffusion_model.py:89-162) on the bit-identical tables: against the
+    reference's outputs (tests/golden/reference_direct.pt) and the oracle's scalar forms"""
     from minimagen_amd.diffusion_model import GaussianDiffusion
     T = 100
     gd = GaussianDiffusion(timesteps=T)
@@ -237,10 +259,8 @@ def test_gaussian_diffusion_public_methods():
         m_ref = sched.q_posterior(x0[i:i + 1], xt[i:i + 1], ti)
         assert torch.equal(mean[i], m_ref[0][0])
     assert gd.q_sample(x0, t).shape == x0.shape                     # noise defaults to randn_like
-    if os.path.isdir("/root/reference/minimagen"):
-        from oracle import ref_loader
-        ref = ref_loader.load_reference()
-        rgd = ref.diffusion_model.GaussianDiffusion(timesteps=T)
-        assert torch.equal(xt, rgd.q_sample(x0, t, eps)) and torch.equal(x0_hat, rgd.predict_start_from_noise(xt, t, eps))
-        for a, b in zip((mean, var, logvar), rgd.q_posterior(x0, xt, t)):
-            assert torch.equal(a, b)
+    from tests import _inputs as I
+    ref = I.load("reference_direct.pt")["diffusion"]              # the reference's GaussianDiffusion(timesteps=100) on the same inputs
+    assert torch.equal(xt, ref["xt"]) and torch.equal(x0_hat, ref["x0_hat"])
+    for a, b in zip((mean, var, logvar), ref["q_posterior"]):
+        assert torch.equal(a, b)

@@ -1,11 +1,10 @@
 """The oracle (oracle/restated.py) against the golden vectors produced by the unmodified
-reference, and -- when /root/reference is present -- against the reference directly."""
+reference (tests/golden/make_golden.py)."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import restated as R
-from oracle import ref_loader
 from tests import _inputs as I
 
 torch.set_num_threads(8)
@@ -121,38 +120,36 @@ def test_resize_properties():
     assert torch.allclose(mid[1:] - mid[:-1], torch.full((15,), 0.5), atol=1e-5)   # cubic reproduces linear ramps
 
 
-@pytest.mark.skipif(not ref_loader.reference_available(), reason="reference only exists in the build container")
 def test_against_reference_directly(sds):
-    ref = ref_loader.load_reference()
-    p = I.unet_params()
-    u0 = ref.Unet(**p["unet0"]); u0.load_state_dict(sds[0]); u0.eval()
+    """the oracle against the unmodified reference's own outputs (tests/golden/reference_direct.pt, make_golden.py reference_direct)"""
+    from minimagen_amd.Unet import Unet
+    g = I.load("reference_direct.pt")
     emb, mask = R.synthetic_text(3, length=40, seed=3)
     x = I.seeded((3, 3, 64, 64), 5)
     time = torch.tensor([0, 24, 7])
-    with torch.no_grad():
-        a = u0.forward_with_cond_scale(x, time, text_embeds=emb, text_mask=mask, cond_scale=3.)
     b = R.unet_forward_with_cond_scale(sds[0], x, time, cond_scale=3., text_embeds=emb, text_mask=mask)
-    assert torch.allclose(a, b, atol=5e-6, rtol=1e-6)
+    assert torch.allclose(g["base_cs3"], b, atol=5e-6, rtol=1e-6)
     # an attention-bearing config (self-attention TransformerBlocks + mid attention)
     torch.manual_seed(3)
-    ua = ref.Unet(dim=16, dim_mults=(1, 2), num_resnet_blocks=1, layer_attns=(False, True), layer_cross_attns=(False, True),
-                  attend_at_middle=True, memory_efficient=False).eval()
+    sd = Unet(dim=16, dim_mults=(1, 2), num_resnet_blocks=1, layer_attns=(False, True), layer_cross_attns=(False, True),
+              attend_at_middle=True, memory_efficient=False).state_dict()
+    assert I.fingerprint(sd) == g["attn"]["fingerprint"], "the seeded weights the reference ran with changed: regenerate the fixture"
     xa = I.seeded((2, 3, 32, 32), 6)
-    with torch.no_grad():
-        a = ua(xa, torch.tensor([3, 9]), text_embeds=emb[:2], text_mask=mask[:2])
-    b = R.unet_forward(ua.state_dict(), xa, torch.tensor([3, 9]), text_embeds=emb[:2], text_mask=mask[:2])
-    assert torch.allclose(a, b, atol=5e-6, rtol=1e-6)
+    b = R.unet_forward(sd, xa, torch.tensor([3, 9]), text_embeds=emb[:2], text_mask=mask[:2])
+    assert torch.allclose(g["attn"]["out"], b, atol=5e-6, rtol=1e-6)
 
 
-@pytest.mark.skipif(not ref_loader.reference_available(), reason="reference only exists in the build container")
 def test_sweep_configs_against_reference_directly():
-    """the constructor-argument sweep of tests/test_unet.py::test_config_sweep_vs_oracle: the oracle equals the unmodified reference"""
+    """the constructor-argument sweep of tests/test_unet.py::test_config_sweep_vs_oracle: the oracle equals the unmodified reference
+    (its outputs on the same seeded weights and inputs, tests/golden/reference_direct.pt)"""
+    from minimagen_amd.Unet import Unet
     from tests.test_unet import SWEEP
-    ref = ref_loader.load_reference()
+    g = I.load("reference_direct.pt")["sweep"]
+    assert sorted(g) == sorted(SWEEP)
     for case, (kw, S, extra) in sorted(SWEEP.items()):
         torch.manual_seed(1)
-        ru = ref.Unet(**kw).eval()
-        sd = {k: v.clone() for k, v in ru.state_dict().items()}
+        sd = Unet(**kw).state_dict()
+        assert I.fingerprint(sd) == g[case]["fingerprint"], case
         E, ch = extra.get("E", 512), extra.get("ch", 3)
         emb, mask = R.synthetic_text(2, length=10, seed=3)
         if E != 512:
@@ -161,10 +158,8 @@ def test_sweep_configs_against_reference_directly():
         kwargs = dict(text_embeds=emb, text_mask=None if extra.get("nomask") else mask)
         if extra.get("lowres"):
             kwargs.update(lowres_cond_img=I.seeded((2, ch, S, S), 7), lowres_noise_times=torch.tensor([5, 5]))
-        with torch.no_grad():
-            a = ru(x, tm, **kwargs)
         b = R.unet_forward(sd, x, tm, **kwargs)
-        assert torch.allclose(a, b, atol=5e-6, rtol=1e-6), case
+        assert torch.allclose(g[case]["out"], b, atol=5e-6, rtol=1e-6), case
 
 
 def test_cubic_resize_interior_matches_pillow_bicubic():

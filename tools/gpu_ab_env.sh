@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 ROOTDIR=$(pwd); TAG=$1; shift; OUT=$ROOTDIR/gpurun_out/$TAG; mkdir -p $OUT
 for spec in "$@"; do
   name=${spec%%:*}; envs=${spec#*:}
-  env $envs timeout 400 python bench.py --steps ${AB_STEPS:-8} --warmup 2 --no-cpu-baseline --no-secondary --no-t5 --breakdown-out $OUT/bd_$name.json > $OUT/bench_$name.json 2> $OUT/bench_$name.err
+  env $envs timeout 400 python bench.py --full --steps ${AB_STEPS:-8} --warmup 2 --no-cpu-baseline --no-secondary --no-t5 --breakdown-out $OUT/bd_$name.json > $OUT/bench_$name.json 2> $OUT/bench_$name.err
   python - <<PY
 import json
 try:

@@ -6,7 +6,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 tag=${1:-ab_lib}; var=${2:?variant name}; out=gpurun_out/$tag; mkdir -p $out
 python -m pytest tests/test_conv_stripe.py tests/test_unet.py -x -q -m gpu > $out/pytest.log 2>&1; tail -2 $out/pytest.log
-run() { name=$1; shift; env "$@" python bench.py --steps 8 --warmup 2 --no-secondary --no-cpu-baseline --no-t5 --breakdown-out $out/breakdown_$name.json > $out/bench_$name.json 2> $out/bench_$name.err
+run() { name=$1; shift; env "$@" python bench.py --full --steps 8 --warmup 2 --no-secondary --no-cpu-baseline --no-t5 --breakdown-out $out/breakdown_$name.json > $out/bench_$name.json 2> $out/bench_$name.err
 python - <<P
 import json
 try:

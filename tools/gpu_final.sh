@@ -6,9 +6,9 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 ROOTDIR=$(pwd); TAG=${1:-final}; OUT=$ROOTDIR/gpurun_out; mkdir -p $OUT
 timeout 1800 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.log
-timeout 900 python bench.py --breakdown-out $OUT/bd_cascade.json > $OUT/bench_cascade.log 2> $OUT/bench_cascade.err; echo "bench rc=$?"; tail -1 $OUT/bench_cascade.log | cut -c1-300
-timeout 300 python bench.py --precision half --no-cpu-baseline --no-secondary --no-t5 --breakdown-out $OUT/bd_half.json > $OUT/bench_half.log 2>&1; tail -1 $OUT/bench_half.log | cut -c1-200
-timeout 300 python bench.py --workload base64 --no-cpu-baseline --no-secondary --no-t5 --breakdown-out $OUT/bd_base.json > $OUT/bench_base.log 2>&1; tail -1 $OUT/bench_base.log | cut -c1-200
+timeout 900 python bench.py --full --breakdown-out $OUT/bd_cascade.json > $OUT/bench_cascade.log 2> $OUT/bench_cascade.err; echo "bench rc=$?"; tail -1 $OUT/bench_cascade.log | cut -c1-300
+timeout 300 python bench.py --full --precision half --no-cpu-baseline --no-secondary --no-t5 --breakdown-out $OUT/bd_half.json > $OUT/bench_half.log 2>&1; tail -1 $OUT/bench_half.log | cut -c1-200
+timeout 300 python bench.py --full --workload base64 --no-cpu-baseline --no-secondary --no-t5 --breakdown-out $OUT/bd_base.json > $OUT/bench_base.log 2>&1; tail -1 $OUT/bench_base.log | cut -c1-200
 timeout 200 python tools/bench_sampler_tail.py 256 32 > $OUT/ubench_sampler_tail.txt 2>&1
 timeout 100 python tools/bench_ce.py > $OUT/ubench_crossembed.txt 2>&1
 CMD="python $ROOTDIR/bench.py --steps 1 --warmup 0 --timesteps 25 --no-cpu-baseline --no-secondary --no-breakdown --no-t5 --no-pipeline"

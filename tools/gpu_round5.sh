@@ -7,7 +7,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 1500 python -m pytest tests -m gpu -q --maxfail=20 -p no:cacheprovider > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -4 $OUT/pytest_gpu.log
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-  timeout 900 python bench.py --steps 16 --warmup 3 --breakdown-out $OUT/bench_breakdown_stage1_256.json > $OUT/bench_cascade64_256_n1.json 2> $OUT/bench.err; echo "bench rc=$?"
+  timeout 900 python bench.py --full --steps 16 --warmup 3 --breakdown-out $OUT/bench_breakdown_stage1_256.json > $OUT/bench_cascade64_256_n1.json 2> $OUT/bench.err; echo "bench rc=$?"
   python - <<PY
 import json
 try:

@@ -19,7 +19,7 @@ done
 } > $out/conv_isolated.txt 2>&1
 cat $out/conv_isolated.txt
 for v in $variants; do
-  MINIMAGEN_CONV_STRIPE=$v python bench.py --steps 6 --warmup 2 --no-secondary --no-cpu-baseline --no-t5 --breakdown-out $out/breakdown_stripe_$v.json > $out/bench_stripe_$v.json 2> $out/bench_stripe_$v.err
+  MINIMAGEN_CONV_STRIPE=$v python bench.py --full --steps 6 --warmup 2 --no-secondary --no-cpu-baseline --no-t5 --breakdown-out $out/breakdown_stripe_$v.json > $out/bench_stripe_$v.json 2> $out/bench_stripe_$v.err
   python - <<P
 import json
 d=json.loads([l for l in open("$out/bench_stripe_$v.json") if l.startswith("{")][-1])
