@@ -549,6 +549,33 @@ typedef struct mi_folded_attn_params {
 int mi_folded_attn_fwd(const mi_folded_attn_params* p, void* stream);
 int mi_folded_attn_bwd(const mi_folded_attn_params* p, void* stream);
 
+/* the core of the wide presets' attention layers in the training graph (dim_head 64: the multi-query Attention, layers.py:52-104, and the
+ * unfolded CrossAttention, layers.py:220-251), forward and backward without the [queries x context] score tensor:
+ *   out[b][i][64h:64h+64] = sum_j softmax_j(q_scale / log2(e) * q[b][i][64h:64h+64] . k[b][j][64kvh:]) v[b][j][64kvh:]
+ * with kvh = 0 (kv_heads = 1) or h (kv_heads = heads), mask[b][j] == 0: row j takes no part (every query needs one live row; the layers'
+ * null row always is).  The null row and any context rows are concatenated into k / v by the caller.
+ * mi_flash_attn_train_fwd: the inference kernel of mi_flash_attn_fwd (3-term fp16-split products, K / V block-scaled per 64-row chunk), which also
+ *   writes lse; without a mask its output equals mi_flash_attn_fwd's (null_k = NULL, one segment, a kv_prep workspace) to the bit.
+ * mi_flash_attn_train_bwd: dq, dk, dv (FlashAttention-2 structure: scores recomputed from q, k and lse; dk / dv partials over query splits added
+ *   in a fixed order -- deterministic).  Reads q, k, v, mask, out, lse, dout; writes dq, dk, dv (every element). */
+typedef struct mi_flash_attn_train_params {
+    int B, n, heads, kv_heads, J;   /* dim_head 64; kv_heads 1 or heads; J context rows incl. the null row */
+    const float* q; float q_scale;  /* [B][n][heads*64]; q_scale = softmax scale * log2(e) (as mi_flash_attn_params) */
+    const float* k; const float* v; /* [B][J][kv_heads*64] */
+    const uint8_t* mask;            /* [B][J] or NULL */
+    float* out;                     /* [B][n][heads*64]: written by the forward, read by the backward */
+    float* lse;                     /* [B][heads][n]: written by the forward (log2 domain of the q_scale-scaled scores), read by the backward */
+    const float* dout;              /* [B][n][heads*64] (backward) */
+    float* dq;                      /* [B][n][heads*64] (backward) */
+    float* dk; float* dv;           /* [B][J][kv_heads*64] (backward) */
+    void* work; long long work_bytes;   /* device workspace of mi_flash_attn_train_workspace(B, n, heads, kv_heads, J, backward) bytes */
+} mi_flash_attn_train_params;
+int mi_flash_attn_train_fwd(const mi_flash_attn_train_params* p, void* stream);
+int mi_flash_attn_train_bwd(const mi_flash_attn_train_params* p, void* stream);
+/* bytes of the workspace: the forward's prepared K / V image (backward = 0); backward = 1: two prepared images, D = dO . O per (query, head) and
+ * the dk / dv partials of the query splits */
+long long mi_flash_attn_train_workspace(int B, int n, int heads, int kv_heads, int J, int backward);
+
 /* ---- optimiser step of the training path: torch.optim.Adam's update for every tensor of a model in ONE launch ---------------------------
  * (reference: train.py:99-100, training.py:375-377).  `tensors`, `chunk_tensor`, `chunk_off` are DEVICE arrays: one mi_adam_tensor per
  * parameter, and one (tensor index, chunk offset) pair per launched workgroup (chunk k of a tensor covers elements [k * chunk, (k + 1) * chunk)).

@@ -167,6 +167,12 @@ class MiFoldedAttnParams(C.Structure):
                 ("dsum", C.c_void_p), ("dq", C.c_void_p), ("dkf", C.c_void_p), ("dvf", C.c_void_p), ("oh", C.c_void_p)]
 
 
+class MiFlashAttnTrainParams(C.Structure):
+    _fields_ = [("B", C.c_int), ("n", C.c_int), ("heads", C.c_int), ("kv_heads", C.c_int), ("J", C.c_int), ("q", C.c_void_p), ("q_scale", C.c_float),
+                ("k", C.c_void_p), ("v", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p), ("lse", C.c_void_p), ("dout", C.c_void_p),
+                ("dq", C.c_void_p), ("dk", C.c_void_p), ("dv", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_longlong)]
+
+
 class MiAdamTensor(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_longlong)]
 
@@ -185,7 +191,8 @@ class MiPackConv3Desc(C.Structure):
 
 _STRUCTS = {0: MiAct, 1: MiConvParams, 2: MiCrossEmbedParams, 3: MiLinear, 4: MiTextCondParams, 5: MiCondStepParams,
             6: MiAttnFoldParams, 7: MiCrossAttnParams, 8: MiCfgX0Params, 9: MiQuantileParams, 10: MiPosteriorParams,
-            11: MiResizeParams, 12: MiSelfAttnParams, 13: MiChanFFParams, 14: MiFlashAttnParams, 15: MiTokensToNchwParams, 16: MiConvWgradParams, 17: MiBlockBwdParams, 18: MiCrossEmbedWgradParams, 19: MiFoldedAttnParams, 20: MiAdamTensor, 21: MiAdamParams, 22: MiPackConv3Desc}
+            11: MiResizeParams, 12: MiSelfAttnParams, 13: MiChanFFParams, 14: MiFlashAttnParams, 15: MiTokensToNchwParams, 16: MiConvWgradParams, 17: MiBlockBwdParams, 18: MiCrossEmbedWgradParams, 19: MiFoldedAttnParams, 20: MiAdamTensor, 21: MiAdamParams, 22: MiPackConv3Desc,
+            23: MiFlashAttnTrainParams}
 
 _lib = None
 _backend = None
@@ -203,13 +210,16 @@ def _bind(lib):
     vp, i32, i64, u64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float
     for name in ("mi_conv_fwd", "mi_gn_coef_fwd", "mi_crossembed_fwd", "mi_text_cond_fwd", "mi_cond_step_fwd", "mi_attn_fold_rows", "mi_cross_attn_fwd",
                  "mi_cfg_x0_fwd", "mi_quantile_fwd", "mi_posterior_fwd", "mi_resize_fwd", "mi_self_attn_fwd", "mi_chan_ff_fwd",
-                 "mi_flash_attn_fwd", "mi_conv_prep_fwd", "mi_tokens_to_nchw_fwd", "mi_conv_wgrad", "mi_block_bwd", "mi_crossembed_wgrad", "mi_folded_attn_fwd", "mi_folded_attn_bwd", "mi_adam_step"):
+                 "mi_flash_attn_fwd", "mi_conv_prep_fwd", "mi_tokens_to_nchw_fwd", "mi_conv_wgrad", "mi_block_bwd", "mi_crossembed_wgrad", "mi_folded_attn_fwd", "mi_folded_attn_bwd", "mi_adam_step",
+                 "mi_flash_attn_train_fwd", "mi_flash_attn_train_bwd"):
         getattr(lib, name).argtypes = [vp, vp]
         getattr(lib, name).restype = i32
     lib.mi_conv_prep_bytes.argtypes = [i32, i32, i32, i32, i32]
     lib.mi_conv_prep_bytes.restype = C.c_longlong
     lib.mi_flash_kv_prep_bytes.argtypes = [i32, i32]
     lib.mi_flash_kv_prep_bytes.restype = C.c_longlong
+    lib.mi_flash_attn_train_workspace.argtypes = [i32, i32, i32, i32, i32, i32]
+    lib.mi_flash_attn_train_workspace.restype = C.c_longlong
     lib.mi_step_advance.argtypes = [vp, vp, i32, vp]
     lib.mi_step_advance_by.argtypes = [vp, vp, i32, i32, vp]
     lib.mi_sampler_step_small_fwd.argtypes = [vp, vp, vp, vp]

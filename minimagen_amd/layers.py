@@ -7,7 +7,8 @@ Two execution paths share these modules' parameters:
 * **training** (``Imagen.forward`` -> ``Unet.forward`` in train mode with autograd on): the ``forward`` methods below, differentiable
   torch ops on whatever device the parameters live on -- they state each layer's arithmetic once more in the reference's own order of
   operations, so the paths can be tested against each other.  On the GPU ``Block`` (and the plain 3x3 convs / CrossEmbedLayer, see
-  ``Unet._forward_train``) switch to ``minimagen_amd.train_ops``: HIP kernels forward AND backward; ``CrossAttention`` to its folded form.
+  ``Unet._forward_train``) switch to ``minimagen_amd.train_ops``: HIP kernels forward AND backward; ``CrossAttention`` to its folded form
+  (C < dim_head), the multi-query ``Attention`` and the wide ``CrossAttention`` (dim_head 64) to the flash core of ``train_ops.flash_attention``.
 """
 from __future__ import annotations
 
@@ -152,6 +153,8 @@ class Attention(_Container):
         """layers.py:52-104: one key / value head shared by all query heads, a learned null key / value in front"""
         b, n, _ = x.shape
         x = self.norm(x)
+        if torch.is_grad_enabled() and train_ops.flash_attention_supported(x, self.null_kv.shape[-1], attn_bias):
+            return self._forward_flash(x, context, mask)
         q = self.to_q(x).reshape(b, n, self.heads, -1).transpose(1, 2) * self.scale
         k, v = self.to_kv(x).chunk(2, dim=-1)
         if exists(context) and exists(self.to_context):
@@ -167,6 +170,20 @@ class Attention(_Container):
         attn = sim.softmax(dim=-1, dtype=torch.float32)
         out = torch.einsum('bhij,bjd->bhid', attn, v).transpose(1, 2).reshape(b, n, -1)
         return self.to_out(out)
+
+    def _forward_flash(self, x, context=None, mask=None):
+        """the training graph's form on the device for dim_head 64: the same projections, the attention core on train_ops.flash_attention
+        (HIP forward + backward, no [heads x tokens x context] score tensor)"""
+        b = x.shape[0]
+        q = self.to_q(x)                                                            # [b, n, heads * 64], token-major
+        k, v = self.to_kv(x).chunk(2, dim=-1)
+        if exists(context) and exists(self.to_context):
+            ck, cv = self.to_context(context).chunk(2, dim=-1)
+            k, v = torch.cat((ck, k), dim=-2), torch.cat((cv, v), dim=-2)
+        nk, nv = (t.expand(b, 1, -1) for t in self.null_kv.unbind(dim=-2))
+        k, v = torch.cat((nk, k), dim=-2), torch.cat((nv, v), dim=-2)
+        full = F.pad(mask, (1, 0), value=True) if exists(mask) else None
+        return self.to_out(train_ops.flash_attention(q, k, v, full, self.scale))
 
 
 class Block(_Container):
@@ -251,6 +268,13 @@ class CrossAttention(_Container):
         if torch.is_grad_enabled() and train_ops.ENABLED and (x.is_cuda or train_ops.FORCE) and x.shape[-1] < self.dim_head:
             return self._forward_folded(x, context, mask)
         x, context = self.norm(x), self.norm_context(context)
+        if torch.is_grad_enabled() and train_ops.flash_attention_supported(x, self.dim_head):
+            # training on the device: the core on train_ops.flash_attention (a k / v head per head, the null row in front of each)
+            k, v = self.to_kv(context).chunk(2, dim=-1)                             # [b, J0, heads * 64]
+            nk, nv = (t.repeat(self.heads).expand(b, 1, -1) for t in self.null_kv.unbind(dim=-2))
+            k, v = torch.cat((nk, k), dim=-2), torch.cat((nv, v), dim=-2)
+            full = F.pad(mask, (1, 0), value=True) if exists(mask) else None
+            return self.to_out(train_ops.flash_attention(self.to_q(x), k, v, full, self.scale))
         heads = lambda t: t.reshape(b, t.shape[1], self.heads, -1).transpose(1, 2)
         q = heads(self.to_q(x)) * self.scale
         k, v = (heads(t) for t in self.to_kv(context).chunk(2, dim=-1))

@@ -17,8 +17,11 @@
 Weights are re-packed into matrix-core fragments (``mi_pack_conv3``: one launch per weight and direction) when their version counter changes,
 i.e. once per optimiser step; the exponents of all layers come back with one host round trip (``begin_step``).  ``CrossEmbedLayer``: matrix-core forward + ``mi_crossembed_wgrad``.
 ``CrossAttention`` (C < dim_head): the sampler's fold with the core on ``mi_folded_attn_fwd`` /
-``mi_folded_attn_bwd`` (no score tensor, layers.CrossAttention._forward_folded).  Everything else of the training graph (self-attention,
-conditioning, 1x1 / k4s2 convs, LayerNorms) stays on torch ops.  ``gradient all-reduce``: minimagen_amd/distributed.py::allreduce_gradients.
+``mi_folded_attn_bwd`` (no score tensor, layers.CrossAttention._forward_folded).  The wide presets' attention layers (dim_head 64: the
+multi-query ``Attention`` and the unfolded ``CrossAttention``, C >= dim_head): the projections, null row and LayerNorms as before, the core on
+``flash_attention`` -- ``mi_flash_attn_train_fwd`` (the sampler's flash kernel, which also saves the logsumexp) and ``mi_flash_attn_train_bwd``
+(FlashAttention-2 dq and dk / dv kernels, deterministic): no [heads x tokens x context] score tensor, forward or backward
+(MINIMAGEN_FLASH_TRAIN=0: torch ops).  Conditioning and the remaining elementwise work stay on torch ops.  ``gradient all-reduce``: minimagen_amd/distributed.py::allreduce_gradients.
 MINIMAGEN_TRAIN_HIP=0 switches the whole thing off (torch ops only)."""
 from __future__ import annotations
 
@@ -565,6 +568,68 @@ class _FoldedAttnFn(torch.autograd.Function):
 
 def folded_attention(q: torch.Tensor, kf: torch.Tensor, vf: torch.Tensor, mask) -> torch.Tensor:
     return _FoldedAttnFn.apply(q, kf, vf, mask)
+
+
+FLASH_TRAIN = os.environ.get("MINIMAGEN_FLASH_TRAIN", "1") != "0"      # 0: the wide attention layers' core on torch ops (A/B runs)
+
+
+def flash_attention_supported(x: torch.Tensor, dim_head: int, attn_bias=None) -> bool:
+    """mi_flash_attn_train_fwd / _bwd: fp32, dim_head 64, no additive attention bias (the multi-query Attention and the unfolded CrossAttention
+    of Unet() default, Base and Super)"""
+    return (ENABLED and FLASH_TRAIN and x.dtype == torch.float32 and (x.is_cuda or FORCE) and dim_head == 64 and attn_bias is None)
+
+
+class _FlashAttnFn(torch.autograd.Function):
+    """out[b, i, h] = softmax_j(scale * q[b, i, h] . k[b, j, kvh]) v[b, j, kvh] (q [B, n, H * 64] token-major, k / v [B, J, KVH * 64] with the
+    null row and any context rows already in front, KVH = 1 or H) on the HIP kernels of attn_train_wide.hip: the [queries x context] score
+    tensor is never materialised, forward or backward; saved for the backward: q, k, v, the output and the per-(query, head) logsumexp"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, scale):
+        lib = L.lib()
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        L.require_device(q, k, v)
+        B, n, inner = q.shape
+        J = k.shape[1]
+        m8 = None if mask is None else mask.to(torch.uint8).contiguous()
+        out = torch.empty_like(q)
+        lse = torch.empty(B, inner // 64, n, dtype=torch.float32, device=q.device)
+        p = _flash_params(q, k, v, m8, out, lse, scale)
+        work = torch.empty(lib.mi_flash_attn_train_workspace(B, n, p.heads, p.kv_heads, J, 0), dtype=torch.uint8, device=q.device)
+        p.work, p.work_bytes = work.data_ptr(), work.numel()
+        L.check(lib.mi_flash_attn_train_fwd(C.byref(p), L.current_stream()), "mi_flash_attn_train_fwd")
+        ctx.save_for_backward(q, k, v, m8, out, lse)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.lib()
+        q, k, v, m8, out, lse = ctx.saved_tensors
+        dout = dout.contiguous()
+        L.require_device(dout)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        p = _flash_params(q, k, v, m8, out, lse, ctx.scale)
+        p.dout, p.dq, p.dk, p.dv = dout.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+        work = torch.empty(lib.mi_flash_attn_train_workspace(p.B, p.n, p.heads, p.kv_heads, p.J, 1), dtype=torch.uint8, device=q.device)
+        p.work, p.work_bytes = work.data_ptr(), work.numel()
+        L.check(lib.mi_flash_attn_train_bwd(C.byref(p), L.current_stream()), "mi_flash_attn_train_bwd")
+        return dq, dk, dv, None, None
+
+
+def _flash_params(q, k, v, m8, out, lse, scale):
+    p = L.MiFlashAttnTrainParams()
+    p.B, p.n, p.heads, p.kv_heads, p.J = q.shape[0], q.shape[1], q.shape[2] // 64, k.shape[2] // 64, k.shape[1]
+    p.q, p.q_scale, p.k, p.v, p.mask = q.data_ptr(), scale * P.LOG2E, k.data_ptr(), v.data_ptr(), L.ptr(m8)
+    p.out, p.lse = out.data_ptr(), lse.data_ptr()
+    return p
+
+
+def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask, scale: float) -> torch.Tensor:
+    """softmax(scale * q k^T) v per head for dim_head 64: q [B, n, H * 64], k / v [B, J, KVH * 64] (KVH = 1: multi-query; KVH = H: a k / v
+    head per head), mask [B, J] (False: the row takes no part) or None"""
+    assert q.shape[-1] % 64 == 0 and k.shape[-1] in (64, q.shape[-1]) and v.shape == k.shape, (q.shape, k.shape, v.shape)
+    return _FlashAttnFn.apply(q, k, v, mask, scale)
 
 
 def layer_norm_supported(x: torch.Tensor, weight) -> bool:
