@@ -352,6 +352,33 @@ int mi_step_advance_by(int* t_state, int64_t* times, int B, int n, void* stream)
 /* t = value ; times[b] = value */
 int mi_step_set(int* t_state, int64_t* times, int B, int value, void* stream);
 
+/* ---- sampling in fewer steps than the schedule has (strided DDPM / DDIM / DPM-Solver++ 2M).  The caller walks S <= T steps over a
+ * subsequence of the trained timesteps: the coefficient table has S rows (columns 0..4 as before: x0 = row[0]*x_t - row[1]*eps, then
+ * row[2], row[3], row[4] on the thresholded x0, x_t and the noise draw; column 5 the coefficient of the PREVIOUS step's thresholded x0,
+ * 0 for the one-step solvers), mi_posterior_params.T = S, and *t_state is the STEP index k = S-1 .. 0 --
+ * the table row, the noise index and the Philox stream all stay relative to k.  Only the U-Net's conditioning needs the trained timestep.
+ * Struct index 24 of mi_struct_size; added within ABI 12 (no existing struct or entry changed). */
+typedef struct mi_sampler_ext_params {
+    const int* t_map;             /* [S] step index -> trained timestep (the mapped step kernels); not read by the tail kernels */
+    float* x0_prev;               /* [B][n] the previous step's thresholded x0: read (times coef column 5) and overwritten with this step's by
+                                     the *_ext_fwd tails.  NULL: no history term -- the *_ext_fwd entries then run the plain kernels.  Zero-fill
+                                     it before the first step (its column 5 is 0, and 0 * garbage must not be NaN). */
+    long long reserved[2];        /* zero */
+} mi_sampler_ext_params;
+/* the three tails with the history term; with row = coef + 8 * step, per element, every operation rounded on its own, in this order
+ * (identical in the three forms):
+ *   mean = row[2]*x0 + row[3]*x_t ; mean = mean + row[5]*x0_prev ; x = mean + row[4]*z ; x0_prev = x0      (x0: thresholded) */
+int mi_posterior_ext_fwd(const mi_posterior_params* p, const mi_sampler_ext_params* e, void* stream);
+int mi_sampler_step_small_ext_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* stream);
+int mi_sampler_step_group_ext_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* sync,
+                                  void* stream);
+/* mi_step_set / mi_step_advance / mi_step_advance_by on the step index k, with times[b] = e->t_map[k].  The length S of t_map is not
+ * passed: the CALLER guarantees 0 <= value < S and that the advances never move k above S-1 (n > 0; value < 0 and n <= 0 are rejected).
+ * An advance behind step 0 leaves k < 0 and times at t_map[0]; nothing may read the state then before the next mi_step_set_mapped. */
+int mi_step_set_mapped(int* t_state, int64_t* times, int B, int value, const mi_sampler_ext_params* e, void* stream);
+int mi_step_advance_mapped(int* t_state, int64_t* times, int B, const mi_sampler_ext_params* e, void* stream);
+int mi_step_advance_by_mapped(int* t_state, int64_t* times, int B, int n, const mi_sampler_ext_params* e, void* stream);
+
 /* N(0,1) fill with the same generator as mi_posterior_fwd (x_T, low-res augmentation noise) */
 int mi_randn_fill(float* out, int B, int n, uint64_t seed, int sample0, int stream_id, void* stream);
 

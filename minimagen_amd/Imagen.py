@@ -30,6 +30,9 @@ SAMPLE_LANES = max(1, int(os.environ.get("MINIMAGEN_SAMPLE_LANES", "2")))     # 
 # 1: a synchronous sample() waits on the HOST for its last stage and checks the cooperative kernels' status words before it returns (the
 # default defers the check to the next API entry: the failed call's images are NaN -- fail-stop -- so nothing plausible-but-wrong escapes)
 STRICT_STATUS = os.environ.get("MINIMAGEN_STRICT_STATUS", "0") != "0"
+# sampler stage states kept per workspace for calls with sample_steps / sampler / sampler_eta (one per (T, S, sampler, eta): coefficient
+# table, step tables of S x B2 rows, history buffer, up to 8 graphs); the least recently used one goes when a new setting arrives
+MAX_SOLVER_STATES = max(1, int(os.environ.get("MINIMAGEN_SOLVER_STATES", "8")))
 _STAGE_STREAMS = {}          # (device, lanes, stages, priority mode) -> [lane][stage] HIP streams, process-wide (see sample())
 
 
@@ -160,15 +163,39 @@ class Imagen(nn.Module):
                               lowres_cond_img=lowres_cond_img, lowres_aug_times=lowres_aug_times)
 
     # ------------------------------------------------------------------ sampling
-    def _stage_state(self, ws, sched: GaussianDiffusion, B: int, n: int):
+    def _stage_state(self, ws, sched: GaussianDiffusion, B: int, n: int, solver=None, eng=None):
         # the state (and the step graphs cached on it) lives on the workspace, so it dies with the buffers it points into
+        # ``solver`` = (S, sampler, eta) of a call that samples in fewer steps / with another solver: a state of its own per setting (table,
+        # step -> timestep map, device-resident step, history buffer, graphs); None: the reference's loop, keyed by T as ever
         store = ws.__dict__.setdefault("sampler_state", {})
-        key = sched.num_timesteps
+        key = sched.num_timesteps if solver is None else (sched.num_timesteps,) + tuple(solver)
         st = store.get(key)
+        if st is not None and solver is not None:
+            store[key] = store.pop(key)                      # most recently used last
+        if st is None and solver is not None:
+            # bounded: a caller sweeping S or eta must not grow device memory without limit.  The evicted state's graphs may still be
+            # queued on a stage stream (sample() never host-syncs): drain the device before its buffers and graph handles go (a status
+            # word still to be polled keeps its state object alive through the pending list)
+            solver_keys = [k for k in store if isinstance(k, tuple)]
+            while len(solver_keys) >= MAX_SOLVER_STATES:
+                if L.backend() == "hip-gfx950":
+                    torch.cuda.synchronize(ws.dev)
+                old = store.pop(solver_keys.pop(0))
+                for entry in getattr(old, "graphs", {}).values():
+                    L.lib().mi_graph_destroy(entry["graph"])
+                if eng is not None:
+                    eng.drop_step_tables(ws, old.t_state)
         if st is None:
             dev = ws.dev
             st = type("StageState", (), {})()
-            st.coef = sched.sampler_coef_table().to(dev).contiguous()
+            if solver is None:
+                st.coef = sched.sampler_coef_table().to(dev).contiguous()
+            else:
+                st.tau, coef = sched.sampler_tables(solver[0], solver[1], solver[2] if solver[1] == 'ddim' else None)
+                st.coef = coef.to(dev).contiguous()
+                st.t_map = st.tau.to(torch.int32).to(dev).contiguous()
+                st.x0_prev = torch.zeros(B, n, dtype=torch.float32, device=dev) if solver[1] == 'dpmpp_2m' else None
+                st.ext = L.MiSamplerExtParams(L.ptr(st.t_map), L.ptr(st.x0_prev))
             st.t_state = torch.zeros(1, dtype=torch.int32, device=dev)
             st.x0 = torch.empty(B, n, dtype=torch.float32, device=dev)
             st.hist = torch.zeros(3 * B * 2 * 2048, dtype=torch.int32, device=dev)
@@ -178,7 +205,7 @@ class Imagen(nn.Module):
         return st
 
     def _stage_begin(self, unet: Unet, shape, *, noise_scheduler: GaussianDiffusion, ws, noise_fn: Callable = None, seed: int = 0,
-                     sample0: int = 0, stage: int = 0):
+                     sample0: int = 0, stage: int = 0, solver=None):
         """Everything of a stage's loop that does not depend on the PREVIOUS stage's image: x_T (Imagen.py:400), the device-resident
         timestep, the per-step conditioning tables of all T steps.  sample() issues it for every stage before the first stage's loop,
         so that a later stage's stream has it done while it waits for its low-resolution input (on-device noise only: injected noise
@@ -188,20 +215,28 @@ class Imagen(nn.Module):
         eng = unet.engine()
         B, Cc, H, W = shape
         n = Cc * H * W
-        T = noise_scheduler.num_timesteps
-        st = self._stage_state(ws, noise_scheduler, B, n)
+        T = noise_scheduler.num_timesteps if solver is None else solver[0]        # steps of the loop (one draw each, for every solver)
+        st = self._stage_state(ws, noise_scheduler, B, n, solver, eng)
         noise_dev = None
         if noise_fn is not None:
             ws.x.copy_(noise_fn(shape))                                          # Imagen.py:400
             noise_dev = torch.stack([noise_fn(shape) for _ in range(T)]).to(ws.dev).contiguous()   # Imagen.py:361, in step order
         else:
             L.check(lib.mi_randn_fill(L.ptr(ws.x), B, n, seed, sample0, (stage << 20) | (1 << 19) | 1, stream), "mi_randn_fill")
-        L.check(lib.mi_step_set(L.ptr(st.t_state), L.ptr(ws.times), B, T - 1, stream), "mi_step_set")
-        eng.prepare_step_tables(ws, T, st.t_state, stream)       # (timestep, text)-only conditioning of all T steps, once
+        if solver is None:
+            L.check(lib.mi_step_set(L.ptr(st.t_state), L.ptr(ws.times), B, T - 1, stream), "mi_step_set")
+            eng.prepare_step_tables(ws, T, st.t_state, stream)       # (timestep, text)-only conditioning of all T steps, once
+        else:
+            # the device-resident state is the STEP index; the U-Net's conditioning sees the trained timestep t_map[step]
+            L.check(lib.mi_step_set_mapped(L.ptr(st.t_state), L.ptr(ws.times), B, T - 1, C.byref(st.ext), stream), "mi_step_set_mapped")
+            if st.x0_prev is not None:
+                st.x0_prev.zero_()                                   # the first step's history coefficient is 0: 0 * stale must not be NaN
+            eng.prepare_step_tables(ws, T, st.t_state, stream, t_map=st.tau)
         return st, noise_dev
 
     def _p_sample_loop(self, unet: Unet, shape, *, noise_scheduler: GaussianDiffusion, ws, cond_scale: float,
-                       noise_fn: Callable = None, seed: int = 0, sample0: int = 0, stage: int = 0, use_graph: bool = True, begun=None):
+                       noise_fn: Callable = None, seed: int = 0, sample0: int = 0, stage: int = 0, use_graph: bool = True, begun=None,
+                       solver=None):
         """Imagen.py:373-420 + :329-370 + :261-326: T replays of
         [U-Net (both guidance halves) -> CFG combine + x0 -> dynamic-threshold quantile -> posterior draw -> t -= 1]."""
         lib = L.lib()
@@ -209,11 +244,17 @@ class Imagen(nn.Module):
         eng = unet.engine()
         B, Cc, H, W = shape
         n = Cc * H * W
-        T = noise_scheduler.num_timesteps
+        # ``solver`` = (S, sampler, eta): S steps over a subsequence of the trained timesteps (GaussianDiffusion.sampler_tables); the loop, the
+        # noise index and the Philox stream count STEPS, so everything below is the reference's loop with T = S but for the mapped step
+        # kernels and, for 'dpmpp_2m', the tail entries that carry the previous step's thresholded x0
+        T = noise_scheduler.num_timesteps if solver is None else solver[0]
         two = ws.B2 != ws.B
         if begun is None:
-            begun = self._stage_begin(unet, shape, noise_scheduler=noise_scheduler, ws=ws, noise_fn=noise_fn, seed=seed, sample0=sample0, stage=stage)
+            begun = self._stage_begin(unet, shape, noise_scheduler=noise_scheduler, ws=ws, noise_fn=noise_fn, seed=seed, sample0=sample0, stage=stage,
+                                      solver=solver)
         st, noise_dev = begun
+        ext = C.byref(st.ext) if solver is not None else None
+        history = solver is not None and st.x0_prev is not None
 
         k_lo, k_hi, w = quantile_rank(n, self.dynamic_thresholding_percentile)
         fused = os.environ.get("MINIMAGEN_SAMPLER_FUSED", "1") != "0"
@@ -228,6 +269,8 @@ class Imagen(nn.Module):
         # the captured graph of one denoising step is cached per (workspace, guidance, threshold, noise mode, shard offset, tail kind):
         # the Philox seed lives in device memory, so replays of later sample() calls need no re-capture
         gkey = (float(cond_scale), two, k_lo, k_hi, w, sample0, stage, T, noise_dev is None, group)
+        if solver is not None:
+            gkey += (tuple(solver),)
         cached = getattr(st, "graphs", None)
         if cached is None:
             cached = st.graphs = {}
@@ -264,15 +307,30 @@ class Imagen(nn.Module):
                 if k not in tails:
                     tails[k] = tail_params(k)
                 c_, p_ = tails[k]
-                if small:
+                if small and history:
+                    L.check(lib.mi_sampler_step_small_ext_fwd(C.byref(c_), C.byref(qp), C.byref(p_), ext, stream), "mi_sampler_step_small_ext_fwd")
+                elif small:
                     L.check(lib.mi_sampler_step_small_fwd(C.byref(c_), C.byref(qp), C.byref(p_), stream), "mi_sampler_step_small_fwd")
+                elif group and history:
+                    L.check(lib.mi_sampler_step_group_ext_fwd(C.byref(c_), C.byref(qp), C.byref(p_), ext, L.ptr(st.group_sync), stream),
+                            "mi_sampler_step_group_ext_fwd")
                 elif group:
                     L.check(lib.mi_sampler_step_group_fwd(C.byref(c_), C.byref(qp), C.byref(p_), L.ptr(st.group_sync), stream), "mi_sampler_step_group_fwd")
                 else:
                     L.check(lib.mi_cfg_x0_fwd(C.byref(c_), stream), "mi_cfg_x0_fwd")
                     L.check(lib.mi_quantile_fwd(C.byref(qp), stream), "mi_quantile_fwd")
-                    L.check(lib.mi_posterior_fwd(C.byref(p_), stream), "mi_posterior_fwd")
-                if advance == 1:
+                    if history:
+                        L.check(lib.mi_posterior_ext_fwd(C.byref(p_), ext, stream), "mi_posterior_ext_fwd")
+                    else:
+                        L.check(lib.mi_posterior_fwd(C.byref(p_), stream), "mi_posterior_fwd")
+                if advance == 0:
+                    return
+                if solver is not None:
+                    if advance == 1:
+                        L.check(lib.mi_step_advance_mapped(L.ptr(st.t_state), L.ptr(ws.times), B, ext, stream), "mi_step_advance_mapped")
+                    else:
+                        L.check(lib.mi_step_advance_by_mapped(L.ptr(st.t_state), L.ptr(ws.times), B, advance, ext, stream), "mi_step_advance_by_mapped")
+                elif advance == 1:
                     L.check(lib.mi_step_advance(L.ptr(st.t_state), L.ptr(ws.times), B, stream), "mi_step_advance")
                 elif advance > 1:
                     L.check(lib.mi_step_advance_by(L.ptr(st.t_state), L.ptr(ws.times), B, advance, stream), "mi_step_advance_by")
@@ -323,6 +381,34 @@ class Imagen(nn.Module):
             self.__dict__.setdefault("_status_stages", []).append((st, stage, (B, H, W)))
         return img
 
+    def _parse_solver(self, sample_steps, sampler, sampler_eta):
+        """Per stage: None (the reference's loop on all T timesteps) or (S, sampler, eta).  Host only; raises ValueError on bad values."""
+        n_stages = len(self.unets)
+        if sampler is not None and sampler not in GaussianDiffusion.SAMPLERS:
+            raise ValueError(f"sampler must be one of {GaussianDiffusion.SAMPLERS}, got {sampler!r}")
+        name = default(sampler, 'ddpm')
+        if sampler_eta is not None:
+            if name != 'ddim':
+                raise ValueError("sampler_eta goes with sampler='ddim' only")
+            if isinstance(sampler_eta, bool) or not isinstance(sampler_eta, (int, float)) or not 0. <= float(sampler_eta) <= 1.:
+                raise ValueError(f"sampler_eta must be a number in [0, 1], got {sampler_eta!r}")
+        eta = {'ddpm': 1., 'ddim': float(default(sampler_eta, 0.)), 'dpmpp_2m': 0.}[name]
+        if isinstance(sample_steps, (list, tuple)):
+            steps = tuple(sample_steps)
+            if len(steps) != n_stages:
+                raise ValueError(f"sample_steps needs one value per stage ({n_stages}), got {len(steps)}")
+        else:
+            steps = (sample_steps,) * n_stages
+        out = []
+        for S, sched in zip(steps, self.noise_schedulers):
+            T = sched.num_timesteps
+            if S is None:
+                S = T
+            if isinstance(S, bool) or not isinstance(S, int) or not 2 <= S <= T:
+                raise ValueError(f"sample_steps must be an int in [2, {T}] for a stage trained with {T} timesteps, got {S!r}")
+            out.append(None if (S == T and name == 'ddpm') else (S, name, eta))
+        return out
+
     def _lowres_conditioning(self, img, image_size: int, ws, lowres_noise_level: float, noise_fn, seed, sample0, stage):
         """Imagen.py:479-485 + :393: cubic resize (reflect pad) -> q_sample at int(T*level) -> *2-1."""
         lib = L.lib()
@@ -364,14 +450,23 @@ class Imagen(nn.Module):
     def sample(self, texts: List[str] = None, text_masks: torch.Tensor = None, text_embeds: torch.Tensor = None,
                cond_scale: float = 1., lowres_sample_noise_level: float = None, return_pil_images: bool = False,
                device: torch.device = None, *, _noise: Callable = None, _seed: int = 1234, _sample_offset: int = 0,
-               _use_graph: bool = True, _precision: str = None, _async: bool = False, _revalidated: bool = False):
+               _use_graph: bool = True, _precision: str = None, _async: bool = False, _revalidated: bool = False,
+               sample_steps: Union[int, List[int], Tuple[int, ...]] = None, sampler: str = None, sampler_eta: float = None):
         """minimagen/Imagen.py:424-510.  Private keyword-only extras (not in the reference): ``_noise(shape)`` injects a
         host noise stream in the reference's draw order (parity runs); otherwise noise is Philox keyed by
         (``_seed``, ``_sample_offset`` + row, stage, step, element) so a sharded batch reproduces the unsharded one;
         ``_precision`` = "fp32" (default) or "half" (single-fp16-term matrix-core contractions, see engine.UnetEngine.precision);
         ``_async=True`` returns without making the caller's stream wait (``self.last_sample_done`` / the returned tensor's ``sample_done`` is THIS call's completion event; ``wait_pending_samples()`` covers every lane): successive
-        calls then pipeline across the per-stage streams (the base stage of the next batch under the super-resolution stage of this one)."""
-        call_args = dict(texts=texts, text_masks=text_masks, text_embeds=text_embeds, cond_scale=cond_scale, lowres_sample_noise_level=lowres_sample_noise_level,
+        calls then pipeline across the per-stage streams (the base stage of the next batch under the super-resolution stage of this one).
+
+        Sampling in fewer steps (keyword-only, not in the reference): ``sample_steps`` = S, an int or one int per stage, 2 <= S <= T of
+        that stage's schedule (None: T) walks S of the trained timesteps, tau_k = round(k (T-1) / (S-1)), one U-Net evaluation each.
+        ``sampler`` = 'ddpm' (default: the reference's ancestral step on the subsequence), 'ddim' (eta = ``sampler_eta``, default 0) or
+        'dpmpp_2m' (DPM-Solver++ 2M on the thresholded x0, deterministic); ``sampler_eta`` in [0, 1] goes with 'ddim' only.  A call with
+        none of them, or with S = T and 'ddpm', IS the reference's loop (same tables, graphs and kernels as before these arguments
+        existed).  Tables: GaussianDiffusion.sampler_tables.  Bad values raise ValueError before anything is launched."""
+        solvers = self._parse_solver(sample_steps, sampler, sampler_eta)
+        call_args = dict(sample_steps=sample_steps, sampler=sampler, sampler_eta=sampler_eta, texts=texts, text_masks=text_masks, text_embeds=text_embeds, cond_scale=cond_scale, lowres_sample_noise_level=lowres_sample_noise_level,
                          return_pil_images=return_pil_images, device=device, _noise=_noise, _seed=_seed, _sample_offset=_sample_offset,
                          _use_graph=_use_graph, _precision=_precision, _async=_async)
         device = default(device, self.device)
@@ -465,7 +560,7 @@ class Imagen(nn.Module):
                     ws.lowres_times.fill_(int(self.lowres_noise_schedule.num_timesteps * lowres_sample_noise_level))
                 if _noise is None:
                     begun[stage] = self._stage_begin(unet, (batch_size, self.channels, image_size, image_size), noise_scheduler=noise_scheduler,
-                                                     ws=ws, seed=_seed, sample0=_sample_offset, stage=stage)
+                                                     ws=ws, seed=_seed, sample0=_sample_offset, stage=stage, solver=solvers[stage])
         # ---- pass 2: the cascade
         img, prev_done = None, None
         for stage, (unet, channel, image_size, noise_scheduler) in stages:
@@ -479,7 +574,7 @@ class Imagen(nn.Module):
                     self._lowres_conditioning(img, image_size, ws, lowres_sample_noise_level, _noise, _seed, _sample_offset, stage)
                 img = self._p_sample_loop(unet, (batch_size, self.channels, image_size, image_size), noise_scheduler=noise_scheduler,
                                           ws=ws, cond_scale=cond_scale, noise_fn=_noise, seed=_seed, sample0=_sample_offset,
-                                          stage=stage, use_graph=_use_graph, begun=begun.get(stage))
+                                          stage=stage, use_graph=_use_graph, begun=begun.get(stage), solver=solvers[stage])
                 if on_gpu:
                     prev_done = streams[stage].record_event()
         pack_tokens = [] if (_noise is not None or _revalidated) else [(unet.engine(), unet.engine().pack_begin()) for unet in self.unets]

@@ -225,19 +225,30 @@ __global__ __launch_bounds__(256) void randn_fill_kernel(float* out, int n, unsi
 }
 
 // ------------------------------------------------------------------ K13
-__global__ __launch_bounds__(256) void posterior_kernel(const mi_posterior_params p) {
+// HISTORY (the three tail kernels): the multistep solvers' term c5 * (the PREVIOUS step's thresholded x0), coefficient column 5, and the
+// store of this step's thresholded x0 for the next one.  The history kernels take the extension struct as one more argument; the
+// <false> instantiations have the argument list -- and the instructions -- of the kernels before the template parameter existed.
+__device__ __forceinline__ float* x0_prev_of() { return nullptr; }
+__device__ __forceinline__ float* x0_prev_of(const mi_sampler_ext_params& e) { return e.x0_prev; }
+
+template <bool HISTORY, typename... EXT>
+__global__ __launch_bounds__(256) void posterior_kernel(const mi_posterior_params p, const EXT... ext) {
+    static_assert(sizeof...(EXT) == (HISTORY ? 1 : 0), "the history kernels take mi_sampler_ext_params");
     const int b = blockIdx.y;
     const int t = *p.t_state - p.t_off;
     const float c1 = p.coef[t * 8 + 2], c2 = p.coef[t * 8 + 3], sigma = p.coef[t * 8 + 4];
+    const float c5 = HISTORY ? p.coef[t * 8 + 5] : 0.0f;
+    float* const prev = x0_prev_of(ext...);
     const float sq = p.s_q[b];
     const float s = (sq < 1.0f) ? 1.0f : sq;                                     // Imagen.py:320 clamp_(min=1.): a NaN threshold stays NaN, as in torch
     const int k = (p.T - 1) - t;
     const float* nz = p.noise ? p.noise + ((size_t)k * p.B + b) * p.n : nullptr;
     const int nq = (p.n + 3) / 4;
     const bool vec = (p.n & 3) == 0;
-    auto one = [&](float x0, float x, float z) {
+    auto one = [&](float x0, float x, float z, float& pv) {
         x0 = __fdiv_rn(x0 != x0 ? x0 : fminf(fmaxf(x0, -s), s), s);               // Imagen.py:323 (torch.clamp propagates NaN)
-        const float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, x));          // diffusion_model.py:118-121
+        float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, x));                // diffusion_model.py:118-121
+        if constexpr (HISTORY) { mean = __fadd_rn(mean, __fmul_rn(c5, pv)); pv = x0; }
         return __fadd_rn(mean, __fmul_rn(sigma, z));                               // Imagen.py:370
     };
     for (int qd = blockIdx.x * 256 + threadIdx.x; qd < nq; qd += gridDim.x * 256) {
@@ -254,14 +265,20 @@ __global__ __launch_bounds__(256) void posterior_kernel(const mi_posterior_param
         if (vec) {
             const size_t o = (size_t)b * p.n + 4 * qd;
             const float4 x0 = mi_ldg4(p.x0 + o), x = mi_ldg4(p.x + o);
-            mi_stg4(p.x + o, make_float4(one(x0.x, x.x, z[0]), one(x0.y, x.y, z[1]), one(x0.z, x.z, z[2]), one(x0.w, x.w, z[3])));
+            float4 pv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if constexpr (HISTORY) pv = mi_ldg4(prev + o);
+            mi_stg4(p.x + o, make_float4(one(x0.x, x.x, z[0], pv.x), one(x0.y, x.y, z[1], pv.y), one(x0.z, x.z, z[2], pv.z), one(x0.w, x.w, z[3], pv.w)));
+            if constexpr (HISTORY) mi_stg4(prev + o, pv);
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int i = 4 * qd + e;
                 if (i < p.n) {
                     const size_t o = (size_t)b * p.n + i;
-                    p.x[o] = one(p.x0[o], p.x[o], z[e]);
+                    float pv = 0.0f;
+                    if constexpr (HISTORY) pv = prev[o];
+                    p.x[o] = one(p.x0[o], p.x[o], z[e], pv);
+                    if constexpr (HISTORY) prev[o] = pv;
                 }
             }
         }
@@ -275,7 +292,9 @@ __global__ __launch_bounds__(256) void posterior_kernel(const mi_posterior_param
 #define SS_THREADS 1024
 #endif
 constexpr int SS_NT = SS_THREADS, SS_MAXQ = MI_SAMPLER_SMALL_N / 4 / SS_NT;      // quads per work-item
-__global__ __launch_bounds__(SS_NT) void sampler_small_kernel(const mi_cfg_x0_params c, const mi_quantile_params q, const mi_posterior_params pp) {
+template <bool HISTORY, typename... EXT>
+__global__ __launch_bounds__(SS_NT) void sampler_small_kernel(const mi_cfg_x0_params c, const mi_quantile_params q, const mi_posterior_params pp, const EXT... ext) {
+    static_assert(sizeof...(EXT) == (HISTORY ? 1 : 0), "the history kernels take mi_sampler_ext_params");
     __shared__ unsigned lh[2][MI_Q_BINS];
     __shared__ int scratch[8];
     __shared__ unsigned nan_sh;
@@ -283,6 +302,8 @@ __global__ __launch_bounds__(SS_NT) void sampler_small_kernel(const mi_cfg_x0_pa
     const int t = *c.t_state - c.t_off;
     const float ca = c.coef[t * 8 + 0], cb = c.coef[t * 8 + 1];
     const float c1 = c.coef[t * 8 + 2], c2 = c.coef[t * 8 + 3], sigma = c.coef[t * 8 + 4];
+    const float c5 = HISTORY ? c.coef[t * 8 + 5] : 0.0f;
+    float* const prev = x0_prev_of(ext...);
     const bool vec = (n & 3) == 0;
     const size_t ob = (size_t)b * n, on = (size_t)(b + c.B) * n;
     float x0v[SS_MAXQ][4], xtv[SS_MAXQ][4];
@@ -376,18 +397,31 @@ __global__ __launch_bounds__(SS_NT) void sampler_small_kernel(const mi_cfg_x0_pa
         } else {
             randn4(pp.seed_dev ? *pp.seed_dev : pp.seed, (unsigned)(pp.sample0 + b), (unsigned)(pp.stream_base + k), (unsigned)qd, z);
         }
-        float r[4];
+        float r[4], pv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (HISTORY) {
+            if (vec) { const float4 v = mi_ldg4(prev + ob + 4 * qd); pv[0] = v.x; pv[1] = v.y; pv[2] = v.z; pv[3] = v.w; }
+            else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) if (4 * qd + e < n) pv[e] = prev[ob + 4 * qd + e];
+            }
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float x0 = x0v[u][e];
             x0 = __fdiv_rn(x0 != x0 ? x0 : fminf(fmaxf(x0, -s), s), s);                  // Imagen.py:323 (torch.clamp propagates NaN)
-            const float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, xtv[u][e]));     // diffusion_model.py:118-121
+            float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, xtv[u][e]));           // diffusion_model.py:118-121
+            if constexpr (HISTORY) { mean = __fadd_rn(mean, __fmul_rn(c5, pv[e])); pv[e] = x0; }
             r[e] = __fadd_rn(mean, __fmul_rn(sigma, z[e]));                               // Imagen.py:370
         }
-        if (vec) mi_stg4(pp.x + ob + 4 * qd, make_float4(r[0], r[1], r[2], r[3]));
-        else {
+        if (vec) {
+            mi_stg4(pp.x + ob + 4 * qd, make_float4(r[0], r[1], r[2], r[3]));
+            if constexpr (HISTORY) mi_stg4(prev + ob + 4 * qd, make_float4(pv[0], pv[1], pv[2], pv[3]));
+        } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) if (4 * qd + e < n) pp.x[ob + 4 * qd + e] = r[e];
+            for (int e = 0; e < 4; ++e) if (4 * qd + e < n) {
+                pp.x[ob + 4 * qd + e] = r[e];
+                if constexpr (HISTORY) prev[ob + 4 * qd + e] = pv[e];
+            }
         }
     }
 }
@@ -397,6 +431,17 @@ __global__ void step_advance_kernel(int* t_state, long long* times, int B, int s
     __syncthreads();
     for (int b = threadIdx.x; b < B; b += blockDim.x) times[b] = (long long)t;
     if (threadIdx.x == 0) *t_state = t;
+}
+
+// the same with a step -> trained-timestep map: *t_state stays the STEP index k (what the coefficient table, the step tables and the noise
+// are indexed by), the U-Net's conditioning sees times[b] = t_map[k].  Past the last step (k < 0: the advance behind step 0) times keep
+// t_map[0]; nothing reads them before the next mi_step_set_mapped.
+__global__ void step_advance_mapped_kernel(int* t_state, long long* times, int B, int set, int value, const int* t_map) {
+    const int k = set == 1 ? value : (*t_state - (set == 2 ? value : 1));
+    __syncthreads();
+    const long long t = (long long)t_map[k < 0 ? 0 : k];
+    for (int b = threadIdx.x; b < B; b += blockDim.x) times[b] = t;
+    if (threadIdx.x == 0) *t_state = k;
 }
 
 __global__ __launch_bounds__(256) void finalize_kernel(const float* x, float* out, long long total, int unnormalize) {
@@ -472,7 +517,9 @@ __host__ __device__ inline sg_layout sg_sync_layout(int B) {
     return l;
 }
 
-__global__ __launch_bounds__(SG_NT) void sampler_group_kernel(const mi_cfg_x0_params c, const mi_quantile_params q, const mi_posterior_params pp, char* sync, const int G) {
+template <bool HISTORY, typename... EXT>
+__global__ __launch_bounds__(SG_NT) void sampler_group_kernel(const mi_cfg_x0_params c, const mi_quantile_params q, const mi_posterior_params pp, char* sync, const int G, const EXT... ext) {
+    static_assert(sizeof...(EXT) == (HISTORY ? 1 : 0), "the history kernels take mi_sampler_ext_params");
     __shared__ unsigned lh[2][MI_Q_BINS];
     __shared__ __attribute__((aligned(16))) unsigned hc[2][MI_Q_BINS];
     __shared__ int scratch[8];
@@ -506,6 +553,8 @@ __global__ __launch_bounds__(SG_NT) void sampler_group_kernel(const mi_cfg_x0_pa
     const int t = *c.t_state - c.t_off;
     const float ca = c.coef[t * 8 + 0], cb = c.coef[t * 8 + 1];
     const float c1 = c.coef[t * 8 + 2], c2 = c.coef[t * 8 + 3], sigma = c.coef[t * 8 + 4];
+    const float c5 = HISTORY ? c.coef[t * 8 + 5] : 0.0f;
+    float* const prev = x0_prev_of(ext...);
     const size_t ob = (size_t)b * n, on = (size_t)(b + c.B) * n;
     const int q0 = g * SG_NT * SG_MAXQ;                        // this workgroup's quads: q0 + tid + u * SG_NT
     // fail-stop: this workgroup's part of the image becomes NaN (never a stale or half-finished x_t)
@@ -625,15 +674,18 @@ __global__ __launch_bounds__(SG_NT) void sampler_group_kernel(const mi_cfg_x0_pa
         float z[4];
         if (nz) { const float4 v = mi_ldg4(nz + 4 * qd); z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w; }
         else randn4(pp.seed_dev ? *pp.seed_dev : pp.seed, (unsigned)(pp.sample0 + b), (unsigned)(pp.stream_base + k), (unsigned)qd, z);
-        float r[4];
+        float r[4], pv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (HISTORY) { const float4 v = mi_ldg4(prev + ob + 4 * qd); pv[0] = v.x; pv[1] = v.y; pv[2] = v.z; pv[3] = v.w; }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float x0 = x0v[u][e];
             x0 = __fdiv_rn(x0 != x0 ? x0 : fminf(fmaxf(x0, -s), s), s);                  // Imagen.py:323 (torch.clamp propagates NaN)
-            const float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, xtv[u][e]));     // diffusion_model.py:118-121
+            float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, xtv[u][e]));           // diffusion_model.py:118-121
+            if constexpr (HISTORY) { mean = __fadd_rn(mean, __fmul_rn(c5, pv[e])); pv[e] = x0; }
             r[e] = __fadd_rn(mean, __fmul_rn(sigma, z[e]));                               // Imagen.py:370
         }
         mi_stg4(pp.x + ob + 4 * qd, make_float4(r[0], r[1], r[2], r[3]));
+        if constexpr (HISTORY) mi_stg4(prev + ob + 4 * qd, make_float4(pv[0], pv[1], pv[2], pv[3]));
     }
 }
 
@@ -661,15 +713,23 @@ extern "C" int mi_quantile_fwd(const mi_quantile_params* p, void* stream) {
     return mi_check_launch("quantile kernels");
 }
 
-extern "C" int mi_sampler_step_small_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, void* stream) {
+static int sampler_step_small(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* stream) {
     if (c->B <= 0 || c->n <= 0 || q->B != c->B || pp->B != c->B || q->n != c->n || pp->n != c->n) { mi_set_error("mi_sampler_step_small_fwd: inconsistent B / n"); return MI_ERR_INVALID; }
     if (c->n > MI_SAMPLER_SMALL_N) { mi_set_error("mi_sampler_step_small_fwd: n = %d > %d", c->n, MI_SAMPLER_SMALL_N); return MI_ERR_UNSUPPORTED; }
     if (!c->x_t || !c->coef || !c->t_state || !pp->x || c->t_state != pp->t_state || c->t_off != pp->t_off || c->coef != pp->coef || c->x_t != pp->x) {
         mi_set_error("mi_sampler_step_small_fwd: needs x_t == x, one coef table and one t_state / t_off for the step"); return MI_ERR_INVALID;
     }
     if (q->k_lo < 0 || q->k_hi >= q->n || q->k_lo > q->k_hi) { mi_set_error("mi_sampler_step_small_fwd: bad ranks"); return MI_ERR_INVALID; }
-    hipLaunchKernelGGL(sampler_small_kernel, dim3(c->B), dim3(SS_NT), 0, (hipStream_t)stream, *c, *q, *pp);
+    if (e) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_small_kernel<true, mi_sampler_ext_params>), dim3(c->B), dim3(SS_NT), 0, (hipStream_t)stream, *c, *q, *pp, *e);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_small_kernel<false>), dim3(c->B), dim3(SS_NT), 0, (hipStream_t)stream, *c, *q, *pp);
     return mi_check_launch("sampler_small_kernel");
+}
+extern "C" int mi_sampler_step_small_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, void* stream) {
+    return sampler_step_small(c, q, pp, nullptr, stream);
+}
+// the *_ext_fwd entries: with e->x0_prev the history kernels, without it (or without e) exactly the plain entries
+extern "C" int mi_sampler_step_small_ext_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* stream) {
+    return sampler_step_small(c, q, pp, (e && e->x0_prev) ? e : nullptr, stream);
 }
 
 extern "C" int mi_sampler_group_size(int n) {
@@ -680,7 +740,7 @@ extern "C" int mi_sampler_group_size(int n) {
 extern "C" long long mi_sampler_group_sync_bytes(int B, int n) {
     return (B > 0 && mi_sampler_group_size(n) > 0) ? sg_sync_layout(B).total : 0;
 }
-extern "C" int mi_sampler_step_group_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, void* sync, void* stream) {
+static int sampler_step_group(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* sync, void* stream) {
     if (c->B <= 0 || c->n <= 0 || q->B != c->B || pp->B != c->B || q->n != c->n || pp->n != c->n) { mi_set_error("mi_sampler_step_group_fwd: inconsistent B / n"); return MI_ERR_INVALID; }
     const int G = mi_sampler_group_size(c->n);
     if (!G) { mi_set_error("mi_sampler_step_group_fwd: n = %d unsupported (a multiple of 4, at most %d)", c->n, 256 * SG_NT * SG_MAXQ * 4); return MI_ERR_UNSUPPORTED; }
@@ -689,13 +749,26 @@ extern "C" int mi_sampler_step_group_fwd(const mi_cfg_x0_params* c, const mi_qua
         mi_set_error("mi_sampler_step_group_fwd: needs x_t == x, one coef table and one t_state / t_off for the step"); return MI_ERR_INVALID;
     }
     if (q->k_lo < 0 || q->k_hi >= q->n || q->k_lo > q->k_hi) { mi_set_error("mi_sampler_step_group_fwd: bad ranks"); return MI_ERR_INVALID; }
-    hipLaunchKernelGGL(sampler_group_kernel, dim3(c->B * G), dim3(SG_NT), 0, (hipStream_t)stream, *c, *q, *pp, (char*)sync, G);
+    if (e) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_group_kernel<true, mi_sampler_ext_params>), dim3(c->B * G), dim3(SG_NT), 0, (hipStream_t)stream, *c, *q, *pp, (char*)sync, G, *e);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_group_kernel<false>), dim3(c->B * G), dim3(SG_NT), 0, (hipStream_t)stream, *c, *q, *pp, (char*)sync, G);
     return mi_check_launch("sampler_group_kernel");
+}
+extern "C" int mi_sampler_step_group_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, void* sync, void* stream) {
+    return sampler_step_group(c, q, pp, nullptr, sync, stream);
+}
+extern "C" int mi_sampler_step_group_ext_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* sync, void* stream) {
+    return sampler_step_group(c, q, pp, (e && e->x0_prev) ? e : nullptr, sync, stream);
 }
 
 extern "C" int mi_posterior_fwd(const mi_posterior_params* p, void* stream) {
     if (p->B <= 0 || p->n <= 0) { mi_set_error("mi_posterior_fwd: empty"); return MI_ERR_INVALID; }
-    hipLaunchKernelGGL(posterior_kernel, dim3(grid_for((p->n + 3) / 4, 256), p->B), dim3(256), 0, (hipStream_t)stream, *p);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(posterior_kernel<false>), dim3(grid_for((p->n + 3) / 4, 256), p->B), dim3(256), 0, (hipStream_t)stream, *p);
+    return mi_check_launch("posterior_kernel");
+}
+extern "C" int mi_posterior_ext_fwd(const mi_posterior_params* p, const mi_sampler_ext_params* e, void* stream) {
+    if (!e || !e->x0_prev) return mi_posterior_fwd(p, stream);
+    if (p->B <= 0 || p->n <= 0) { mi_set_error("mi_posterior_ext_fwd: empty"); return MI_ERR_INVALID; }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(posterior_kernel<true, mi_sampler_ext_params>), dim3(grid_for((p->n + 3) / 4, 256), p->B), dim3(256), 0, (hipStream_t)stream, *p, *e);
     return mi_check_launch("posterior_kernel");
 }
 
@@ -710,6 +783,23 @@ extern "C" int mi_step_advance_by(int* t_state, int64_t* times, int B, int n, vo
 extern "C" int mi_step_set(int* t_state, int64_t* times, int B, int value, void* stream) {
     hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t_state, (long long*)times, B, 1, value);
     return mi_check_launch("step_advance_kernel");
+}
+
+static int step_mapped(int* t_state, int64_t* times, int B, int set, int value, const mi_sampler_ext_params* e, void* stream) {
+    if (!e || !e->t_map) { mi_set_error("mapped step kernels: t_map missing"); return MI_ERR_INVALID; }
+    hipLaunchKernelGGL(step_advance_mapped_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t_state, (long long*)times, B, set, value, e->t_map);
+    return mi_check_launch("step_advance_mapped_kernel");
+}
+extern "C" int mi_step_advance_mapped(int* t_state, int64_t* times, int B, const mi_sampler_ext_params* e, void* stream) {
+    return step_mapped(t_state, times, B, 0, 0, e, stream);
+}
+extern "C" int mi_step_advance_by_mapped(int* t_state, int64_t* times, int B, int n, const mi_sampler_ext_params* e, void* stream) {
+    if (n <= 0) { mi_set_error("mi_step_advance_by_mapped: n = %d", n); return MI_ERR_INVALID; }
+    return step_mapped(t_state, times, B, 2, n, e, stream);
+}
+extern "C" int mi_step_set_mapped(int* t_state, int64_t* times, int B, int value, const mi_sampler_ext_params* e, void* stream) {
+    if (value < 0) { mi_set_error("mi_step_set_mapped: step %d", value); return MI_ERR_INVALID; }
+    return step_mapped(t_state, times, B, 1, value, e, stream);
 }
 
 extern "C" int mi_randn_fill(float* out, int B, int n, uint64_t seed, int sample0, int stream_id, void* stream) {

@@ -67,6 +67,66 @@ class GaussianDiffusion(nn.Module):
         tab[:, 4] = nonzero * (0.5 * cpu(self.posterior_log_variance_clipped)).exp()
         return tab
 
+    # ---- sampling in S <= T steps over a subsequence of the trained timesteps (not in the reference; DESIGN.md "Fewer sampling steps")
+    SAMPLERS = ('ddpm', 'ddim', 'dpmpp_2m')
+
+    def sampling_timestep_map(self, steps: int) -> torch.Tensor:
+        """tau int64[S]: tau_k = round(k (T-1) / (S-1)) in integer arithmetic -- contains 0 and T-1, strictly increasing, arange(T) for S = T"""
+        T, S = self.num_timesteps, int(steps)
+        if not 2 <= S <= T:
+            raise ValueError(f'sample_steps must be in [2, {T}] for a schedule of {T} timesteps, got {steps}')
+        return torch.tensor([(2 * k * (T - 1) + (S - 1)) // (2 * (S - 1)) for k in range(S)], dtype=torch.int64)
+
+    def _sampler_tables64(self, steps: int, sampler: str = 'ddpm', eta: float = None):
+        """sampler_tables before the rounding to fp32: (tau int64[S], abar float64[S], coef float64[S][8])"""
+        if sampler not in self.SAMPLERS:
+            raise ValueError(f'sampler must be one of {self.SAMPLERS}, got {sampler!r}')
+        if eta is not None and sampler != 'ddim':
+            raise ValueError("sampler_eta goes with sampler='ddim' only")
+        eta = 1. if sampler == 'ddpm' else (0. if eta is None else float(eta))
+        if not 0. <= eta <= 1.:
+            raise ValueError(f'sampler_eta must be in [0, 1], got {eta}')
+        tau = self.sampling_timestep_map(steps)
+        T, S = self.num_timesteps, tau.numel()
+        scale = 1000 / T
+        betas = torch.linspace(scale * 0.0001, scale * 0.02, T, dtype=torch.float64)        # as __init__, kept in fp64
+        a = torch.cumprod(1. - betas, dim=0)[tau]
+        ap = F.pad(a[:-1], (1, 0), value=1.)
+        tab = torch.zeros(S, 8, dtype=torch.float64)
+        tab[:, 0] = torch.sqrt(1. / a)
+        tab[:, 1] = torch.sqrt(1. / a - 1)
+        if sampler != 'dpmpp_2m':
+            # Song et al. 2021 (DDIM), eq. 12 and 16, written on x0: x_{k-1} = sqrt(ap) x0 + sqrt(1 - ap - sigma^2) eps + sigma z
+            sigma = eta * torch.sqrt((1. - ap) / (1. - a)) * torch.sqrt(1. - a / ap)
+            tab[:, 3] = torch.sqrt((1. - ap - sigma ** 2).clamp(min=0.)) / torch.sqrt(1. - a)
+            tab[:, 2] = torch.sqrt(ap) - tab[:, 3] * torch.sqrt(a)
+            tab[:, 4] = sigma
+            tab[0, 4] = 0.
+        else:
+            # Lu et al. 2022 (DPM-Solver++), Algorithm 2 (2M, data prediction) on the thresholded x0
+            al, sg = torch.sqrt(a), torch.sqrt(1. - a)
+            lam = torch.log(al / sg)
+            tab[0, 2] = 1.                                   # the last step returns x0
+            for k in range(1, S):
+                h = lam[k - 1] - lam[k]
+                m = al[k - 1] * (1. - torch.exp(-h))
+                tab[k, 3] = sg[k - 1] / sg[k]
+                if k == S - 1:                               # first step: no history yet (DPM-Solver++ 1 = DDIM)
+                    tab[k, 2] = m
+                else:
+                    r = (lam[k] - lam[k + 1]) / h
+                    tab[k, 2] = m * (1. + 1. / (2. * r))
+                    tab[k, 5] = -m / (2. * r)
+        return tau, a, tab
+
+    def sampler_tables(self, steps: int, sampler: str = 'ddpm', eta: float = None):
+        """(tau int64[S], coef float32[S][8]) for ``steps`` sampling steps over the trained timesteps tau: row k of ``coef`` is the step at
+        timestep tau_k (the sampler walks k = S-1 .. 0).  With cN = column N (the naming of DESIGN.md section 14 and the C header): x0 = c0 x - c1 eps, then
+        x' = c2 x0 + c3 x + c5 x0_prev + c4 z with the thresholded x0 of this and of the previous step.  'ddpm' is 'ddim' with eta = 1 (the reference's ancestral step when
+        S = T); 'dpmpp_2m' is deterministic.  Everything in fp64 from the betas, rounded to fp32 once."""
+        tau, _, tab = self._sampler_tables64(steps, sampler, eta)
+        return tau, tab.to(torch.float32)
+
     # ---- the per-timestep helpers of the reference's public API (diffusion_model.py:89-162).  The sampling hot path has them fused
     # into the HIP sampler kernels (mi_lowres_augment, mi_cfg_x0_fwd, mi_posterior_fwd); these tensor forms serve callers of the class
     # API and the training loss (Imagen.forward), on whatever device the tables live, and are differentiable.

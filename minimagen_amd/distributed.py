@@ -51,7 +51,9 @@ def gather_samples(local: torch.Tensor, batch: int, group=None) -> torch.Tensor:
 def sample_distributed(imagen, *, text_embeds: torch.Tensor, text_masks: Optional[torch.Tensor] = None, gather: bool = True,
                        group=None, **sample_kwargs) -> torch.Tensor:
     """Every rank passes the SAME full-batch ``text_embeds``/``text_masks``; rank r samples rows shard_bounds(B, N, r)
-    and (if ``gather``) all ranks return the full batch."""
+    and (if ``gather``) all ranks return the full batch.  ``sample_kwargs`` go to ``Imagen.sample`` unchanged (``cond_scale``, ``_seed``,
+    ``sample_steps`` / ``sampler`` / ``sampler_eta``, ...): the noise is keyed by the global row, the stage and the STEP index, so the
+    gathered batch equals the unsharded call bit for bit for every solver and step count."""
     ws = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     batch = text_embeds.shape[0]

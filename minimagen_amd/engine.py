@@ -911,25 +911,29 @@ class UnetEngine:
         for fn, p, name in ws.prog_pre:
             L.check(fn(C.byref(p), st), name)
 
-    def prepare_step_tables(self, ws, T: int, t_state: torch.Tensor, stream=None):
+    def prepare_step_tables(self, ws, T: int, t_state: torch.Tensor, stream=None, t_map=None):
         """Once per ``sample()`` stage: the per-step conditioning (every ResnetBlock's scale/shift, the folded time-token rows of the
         cross-attention context) for ALL T timesteps -- the sequence T-1 .. 0 is known in advance and identical for every sample -- so
         that the denoising step only scatters row ``t`` of the tables (one small launch instead of cond_step + fold).  Same kernels,
-        same arithmetic, same bits as the step-at-a-time path."""
+        same arithmetic, same bits as the step-at-a-time path.
+        ``t_map`` (host int64 [T], sampling in fewer steps): the rows are those of the trained timesteps ``t_map[k]`` instead of ``k`` --
+        ``T`` is then the number of sampling steps and ``*t_state`` the step index."""
         u, pk, lib = self.unet, self.packed(), L.lib()
         st = L.current_stream() if stream is None else stream
         B2, dev = ws.B2, ws.dev
         if ws.wide_attn:                 # the wide cross-attention projects the time tokens per step from ws.c_time: keep the per-step conditioning
             ws.prog_stage = ws.prog_cond
             return
-        key = (T, t_state.data_ptr())
+        key = (T, t_state.data_ptr()) if t_map is None else (T, t_state.data_ptr(), tuple(int(v) for v in t_map))
         tb = ws.__dict__.setdefault("step_tables", {}).get(key)
         if tb is None:
             tb = Workspace()
+            steps_t = torch.arange(T, dtype=torch.int64, device=dev) if t_map is None else t_map.to(dev, torch.int64).contiguous()
+            assert steps_t.numel() == T
             n = T * B2
             # per (timestep, batch row): the scale/shift rows (they see the sample's pooled text through t).  Per timestep only: the time
             # tokens of the cross-attention context and their folded (g, v) rows -- identical for every sample, so one row per t.
-            tb.times = torch.arange(T, dtype=torch.int64, device=dev).repeat_interleave(B2).contiguous()
+            tb.times = steps_t.repeat_interleave(B2).contiguous()
             tb.lowres_times = torch.zeros(n, dtype=torch.int64, device=dev) if u.lowres_cond else None
             tb.text_hiddens = torch.empty(n, u.time_cond_dim, dtype=torch.float32, device=dev)
             tb.ss = torch.empty(n, max(pk.R, 1), dtype=torch.float32, device=dev)
@@ -938,7 +942,7 @@ class UnetEngine:
             cp.time, cp.lowres_time = L.ptr(tb.times), L.ptr(tb.lowres_times)
             cp.text_hiddens, cp.ss, cp.c_time, cp.t_out = (L.ptr(tb.text_hiddens) if ws.has_text else 0), L.ptr(tb.ss), 0, 0
             tb.cond = cp
-            tb.times_t = torch.arange(T, dtype=torch.int64, device=dev)
+            tb.times_t = steps_t
             tb.lowres_t = torch.zeros(T, dtype=torch.int64, device=dev) if u.lowres_cond else None
             tb.c_time_t = torch.empty(T, ws.ntot, u.cond_dim, dtype=torch.float32, device=dev)
             ct = L.MiCondStepParams.from_buffer_copy(ws.cond_params)
@@ -978,6 +982,18 @@ class UnetEngine:
         for f1 in tb.fold:
             L.check(lib.mi_attn_fold_rows(C.byref(f1), st), "mi_attn_fold_rows (all steps)")
         ws.prog_stage = tb.stage
+
+    def drop_step_tables(self, ws, t_state: torch.Tensor):
+        """Forget the step tables built for ``t_state`` (a sampler stage state that is being evicted), with the offset copies of their
+        scatter launches (keyed by the identity of the table's launch list, which a later list could inherit).  The caller has drained the device."""
+        tables = ws.__dict__.get("step_tables", {})
+        for key in [k for k in tables if k[1] == t_state.data_ptr()]:
+            tb = tables.pop(key)
+            cache = ws.__dict__.get("prog_stage_off", {})
+            for k in [k for k in cache if k[0] == id(tb.stage)]:
+                del cache[k]
+            if ws.__dict__.get("prog_stage") is tb.stage:
+                ws.prog_stage = ws.prog_cond
 
     def stage_prog(self, ws, t_off: int = 0):
         """The per-step conditioning launches for the step ``*t_state - t_off`` (the steps of one captured graph share one advance of

@@ -79,7 +79,9 @@ def _prepare_output(save_directory: str) -> str:
 def sample_and_save(captions: list, *, minimagen: Optional[Imagen] = None, training_directory: Optional[str] = None,
                     sample_args: dict = {}, save_directory: Optional[str] = None, filetype: str = "png"):
     """generate.py:124-173: writes ``captions.txt`` (+ ``imagen_training_directory.txt``) into ``save_directory`` and
-    ``generated_images/image_<caption index>.<filetype>``; exactly one of ``minimagen`` / ``training_directory``."""
+    ``generated_images/image_<caption index>.<filetype>``; exactly one of ``minimagen`` / ``training_directory``.
+    ``sample_args`` goes to ``Imagen.sample`` as keywords -- ``cond_scale``, and the step-count knobs ``sample_steps`` / ``sampler`` /
+    ``sampler_eta`` (e.g. ``dict(cond_scale=3., sample_steps=25, sampler='dpmpp_2m')``) among them."""
     assert not (minimagen is None and training_directory is None), \
         "Must supply either a training directory or MinImagen instance."
     assert (minimagen is not None) ^ (training_directory is not None), \
