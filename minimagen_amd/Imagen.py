@@ -3,19 +3,18 @@ reverse-diffusion loop runs as HIP kernels replayed from a HIP graph on MI355X."
 from __future__ import annotations
 
 import ctypes as C
-from typing import Callable, List, Literal, Tuple, Union
-
 import os
+from typing import Callable, List, Literal, Tuple, Union
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import _lib as L
+from . import sampler as S
 from .Unet import Unet
 from .diffusion_model import GaussianDiffusion
-from .helpers import (cast_tuple, cubic_taps, default, eval_decorator, exists, module_device, normalize_neg_one_to_one, quantile_rank,
-                      resize_image_to)
+from .helpers import (cast_tuple, cubic_taps, default, eval_decorator, exists, module_device, normalize_neg_one_to_one, resize_image_to)
 from .t5 import get_encoded_dim, t5_encode_text
 
 # the sampler tail of images too large for one workgroup (the super-resolution stages) as ONE launch of cooperating workgroups
@@ -26,13 +25,13 @@ SAMPLER_GROUP = int(os.environ.get("MINIMAGEN_SAMPLER_GROUP", "1"))
 # 1024^2 tails (128 workgroups of 1024 work-items per image, one per CU) in flight on two call lanes starved each other's last image until the
 # bounded spin gave up (profiles/r04_sampler_group_config5.txt) -- large images keep the separate kernels
 SAMPLER_GROUP_MAX = int(os.environ.get("MINIMAGEN_SAMPLER_GROUP_MAX", "8"))
+# sampler stage states kept per workspace for calls with sample_steps / sampler / sampler_eta (one per (T, S, sampler, eta): coefficient
+# table, step tables of S x B2 rows, history buffer, up to 8 graphs); the least recently used one goes when a new setting arrives
+MAX_SOLVER_STATES = max(1, int(os.environ.get("MINIMAGEN_SOLVER_STATES", "8")))
 SAMPLE_LANES = max(1, int(os.environ.get("MINIMAGEN_SAMPLE_LANES", "2")))     # independent call lanes of sample(_async=True)
 # 1: a synchronous sample() waits on the HOST for its last stage and checks the cooperative kernels' status words before it returns (the
 # default defers the check to the next API entry: the failed call's images are NaN -- fail-stop -- so nothing plausible-but-wrong escapes)
 STRICT_STATUS = os.environ.get("MINIMAGEN_STRICT_STATUS", "0") != "0"
-# sampler stage states kept per workspace for calls with sample_steps / sampler / sampler_eta (one per (T, S, sampler, eta): coefficient
-# table, step tables of S x B2 rows, history buffer, up to 8 graphs); the least recently used one goes when a new setting arrives
-MAX_SOLVER_STATES = max(1, int(os.environ.get("MINIMAGEN_SOLVER_STATES", "8")))
 _STAGE_STREAMS = {}          # (device, lanes, stages, priority mode) -> [lane][stage] HIP streams, process-wide (see sample())
 
 
@@ -86,7 +85,7 @@ class Imagen(nn.Module):
         self.dynamic_thresholding_percentile = dynamic_thresholding_percentile
         self.register_buffer('_temp', torch.tensor([0.]), persistent=False)
         self.to(next(self.unets.parameters()).device)
-        self._sampler_state = {}
+        self._status_stages, self._status_pending, self._lane_done = [], [], {}      # see _poll_status / wait_pending_samples
 
     @property
     def device(self) -> torch.device:
@@ -163,223 +162,15 @@ class Imagen(nn.Module):
                               lowres_cond_img=lowres_cond_img, lowres_aug_times=lowres_aug_times)
 
     # ------------------------------------------------------------------ sampling
+    # ------------------------------------------------------------------ sampling (the loop itself: minimagen_amd/sampler.py)
     def _stage_state(self, ws, sched: GaussianDiffusion, B: int, n: int, solver=None, eng=None):
-        # the state (and the step graphs cached on it) lives on the workspace, so it dies with the buffers it points into
-        # ``solver`` = (S, sampler, eta) of a call that samples in fewer steps / with another solver: a state of its own per setting (table,
-        # step -> timestep map, device-resident step, history buffer, graphs); None: the reference's loop, keyed by T as ever
-        store = ws.__dict__.setdefault("sampler_state", {})
-        key = sched.num_timesteps if solver is None else (sched.num_timesteps,) + tuple(solver)
-        st = store.get(key)
-        if st is not None and solver is not None:
-            store[key] = store.pop(key)                      # most recently used last
-        if st is None and solver is not None:
-            # bounded: a caller sweeping S or eta must not grow device memory without limit.  The evicted state's graphs may still be
-            # queued on a stage stream (sample() never host-syncs): drain the device before its buffers and graph handles go (a status
-            # word still to be polled keeps its state object alive through the pending list)
-            solver_keys = [k for k in store if isinstance(k, tuple)]
-            while len(solver_keys) >= MAX_SOLVER_STATES:
-                if L.backend() == "hip-gfx950":
-                    torch.cuda.synchronize(ws.dev)
-                old = store.pop(solver_keys.pop(0))
-                for entry in getattr(old, "graphs", {}).values():
-                    L.lib().mi_graph_destroy(entry["graph"])
-                if eng is not None:
-                    eng.drop_step_tables(ws, old.t_state)
-        if st is None:
-            dev = ws.dev
-            st = type("StageState", (), {})()
-            if solver is None:
-                st.coef = sched.sampler_coef_table().to(dev).contiguous()
-            else:
-                st.tau, coef = sched.sampler_tables(solver[0], solver[1], solver[2] if solver[1] == 'ddim' else None)
-                st.coef = coef.to(dev).contiguous()
-                st.t_map = st.tau.to(torch.int32).to(dev).contiguous()
-                st.x0_prev = torch.zeros(B, n, dtype=torch.float32, device=dev) if solver[1] == 'dpmpp_2m' else None
-                st.ext = L.MiSamplerExtParams(L.ptr(st.t_map), L.ptr(st.x0_prev))
-            st.t_state = torch.zeros(1, dtype=torch.int32, device=dev)
-            st.x0 = torch.empty(B, n, dtype=torch.float32, device=dev)
-            st.hist = torch.zeros(3 * B * 2 * 2048, dtype=torch.int32, device=dev)
-            st.s_q = torch.zeros(B, dtype=torch.float32, device=dev)
-            st.v_q = torch.zeros(B, 2, dtype=torch.float32, device=dev)
-            store[key] = st
-        return st
+        return S.stage_state(ws, sched, B, n, solver, eng, MAX_SOLVER_STATES)
 
-    def _stage_begin(self, unet: Unet, shape, *, noise_scheduler: GaussianDiffusion, ws, noise_fn: Callable = None, seed: int = 0,
-                     sample0: int = 0, stage: int = 0, solver=None):
-        """Everything of a stage's loop that does not depend on the PREVIOUS stage's image: x_T (Imagen.py:400), the device-resident
-        timestep, the per-step conditioning tables of all T steps.  sample() issues it for every stage before the first stage's loop,
-        so that a later stage's stream has it done while it waits for its low-resolution input (on-device noise only: injected noise
-        must be drawn in the reference's order)."""
-        lib = L.lib()
-        stream = L.current_stream()
-        eng = unet.engine()
-        B, Cc, H, W = shape
-        n = Cc * H * W
-        T = noise_scheduler.num_timesteps if solver is None else solver[0]        # steps of the loop (one draw each, for every solver)
-        st = self._stage_state(ws, noise_scheduler, B, n, solver, eng)
-        noise_dev = None
-        if noise_fn is not None:
-            ws.x.copy_(noise_fn(shape))                                          # Imagen.py:400
-            noise_dev = torch.stack([noise_fn(shape) for _ in range(T)]).to(ws.dev).contiguous()   # Imagen.py:361, in step order
-        else:
-            L.check(lib.mi_randn_fill(L.ptr(ws.x), B, n, seed, sample0, (stage << 20) | (1 << 19) | 1, stream), "mi_randn_fill")
-        if solver is None:
-            L.check(lib.mi_step_set(L.ptr(st.t_state), L.ptr(ws.times), B, T - 1, stream), "mi_step_set")
-            eng.prepare_step_tables(ws, T, st.t_state, stream)       # (timestep, text)-only conditioning of all T steps, once
-        else:
-            # the device-resident state is the STEP index; the U-Net's conditioning sees the trained timestep t_map[step]
-            L.check(lib.mi_step_set_mapped(L.ptr(st.t_state), L.ptr(ws.times), B, T - 1, C.byref(st.ext), stream), "mi_step_set_mapped")
-            if st.x0_prev is not None:
-                st.x0_prev.zero_()                                   # the first step's history coefficient is 0: 0 * stale must not be NaN
-            eng.prepare_step_tables(ws, T, st.t_state, stream, t_map=st.tau)
-        return st, noise_dev
+    def _stage_begin(self, unet: Unet, shape, **kw):          # -> (stage state, injected noise)
+        return S.stage_begin(unet, shape, max_states=MAX_SOLVER_STATES, **kw)
 
-    def _p_sample_loop(self, unet: Unet, shape, *, noise_scheduler: GaussianDiffusion, ws, cond_scale: float,
-                       noise_fn: Callable = None, seed: int = 0, sample0: int = 0, stage: int = 0, use_graph: bool = True, begun=None,
-                       solver=None):
-        """Imagen.py:373-420 + :329-370 + :261-326: T replays of
-        [U-Net (both guidance halves) -> CFG combine + x0 -> dynamic-threshold quantile -> posterior draw -> t -= 1]."""
-        lib = L.lib()
-        stream = L.current_stream()
-        eng = unet.engine()
-        B, Cc, H, W = shape
-        n = Cc * H * W
-        # ``solver`` = (S, sampler, eta): S steps over a subsequence of the trained timesteps (GaussianDiffusion.sampler_tables); the loop, the
-        # noise index and the Philox stream count STEPS, so everything below is the reference's loop with T = S but for the mapped step
-        # kernels and, for 'dpmpp_2m', the tail entries that carry the previous step's thresholded x0
-        T = noise_scheduler.num_timesteps if solver is None else solver[0]
-        two = ws.B2 != ws.B
-        if begun is None:
-            begun = self._stage_begin(unet, shape, noise_scheduler=noise_scheduler, ws=ws, noise_fn=noise_fn, seed=seed, sample0=sample0, stage=stage,
-                                      solver=solver)
-        st, noise_dev = begun
-        ext = C.byref(st.ext) if solver is not None else None
-        history = solver is not None and st.x0_prev is not None
-
-        k_lo, k_hi, w = quantile_rank(n, self.dynamic_thresholding_percentile)
-        fused = os.environ.get("MINIMAGEN_SAMPLER_FUSED", "1") != "0"
-        small = n <= 16384 and fused                                    # MI_SAMPLER_SMALL_N: the whole tail in one launch of one workgroup per image
-        # ... or of <= SAMPLER_GROUP_MAX cooperating workgroups per image.  A stage state whose grouped launch ever failed (fail-stop:
-        # NaN images + the sticky error word, see _poll_status) keeps the separate kernels from then on
-        group = (not small) and fused and bool(SAMPLER_GROUP) and 0 < lib.mi_sampler_group_size(n) <= SAMPLER_GROUP_MAX \
-            and not getattr(st, "group_failed", False)
-        if getattr(st, "group_heal", False):
-            st.group_sync.zero_()               # stream-ordered behind every launch queued on this lane: ticket, counters, histograms, error word
-            st.group_heal = False
-        # the captured graph of one denoising step is cached per (workspace, guidance, threshold, noise mode, shard offset, tail kind):
-        # the Philox seed lives in device memory, so replays of later sample() calls need no re-capture
-        gkey = (float(cond_scale), two, k_lo, k_hi, w, sample0, stage, T, noise_dev is None, group)
-        if solver is not None:
-            gkey += (tuple(solver),)
-        cached = getattr(st, "graphs", None)
-        if cached is None:
-            cached = st.graphs = {}
-        entry = cached.get(gkey) if (use_graph and noise_dev is None) else None
-        if noise_dev is None:
-            if not hasattr(st, "seed_dev"):
-                st.seed_dev = torch.zeros(1, dtype=torch.int64, device=ws.dev)
-            st.seed_dev.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
-        if entry is None:
-            # the radix select's first pass rides on the kernel that produces x0, and the histograms clean themselves: st.hist is
-            # zero on allocation and every mi_quantile_fwd leaves it zeroed again
-            cp = L.MiCfgX0Params(B, n, L.ptr(ws.pred), 1 if two else 0, float(cond_scale), L.ptr(ws.x), L.ptr(st.coef), L.ptr(st.t_state), 0, L.ptr(st.x0),
-                                 L.ptr(st.hist))
-            qp = L.MiQuantileParams(B, n, L.ptr(st.x0), k_lo, k_hi, w, L.ptr(st.hist), L.ptr(st.s_q), L.ptr(st.v_q), 1, 1)
-            pp = L.MiPosteriorParams(B, n, T, L.ptr(st.x0), L.ptr(st.s_q), L.ptr(ws.x), L.ptr(st.coef), L.ptr(st.t_state),
-                                     L.ptr(noise_dev), int(seed) & 0x7FFFFFFFFFFFFFFF, sample0, stage << 20,
-                                     L.ptr(st.seed_dev) if noise_dev is None else 0)
-
-            if group and not hasattr(st, "group_sync"):
-                st.group_sync = torch.zeros(lib.mi_sampler_group_sync_bytes(B, n), dtype=torch.uint8, device=ws.dev)   # this workspace's launches only
-                st.group_err_host = torch.zeros(1, dtype=torch.int32).pin_memory() if L.backend() == "hip-gfx950" else torch.zeros(1, dtype=torch.int32)
-            offsets = eng.step_offsets_supported(ws)          # the k-th step of a graph addresses *t_state - k; one advance per graph
-
-            def tail_params(k):
-                c_, p_ = L.MiCfgX0Params.from_buffer_copy(cp), L.MiPosteriorParams.from_buffer_copy(pp)
-                c_.t_off = p_.t_off = k
-                if small or group:
-                    c_.x0 = c_.hist0 = 0                      # x0 stays in registers, the histograms in LDS (and per-image counters)
-                return c_, p_
-            tails = {}
-
-            def one_step(k=0, advance=1):
-                eng.run_step(ws, stream, t_off=k)
-                if k not in tails:
-                    tails[k] = tail_params(k)
-                c_, p_ = tails[k]
-                if small and history:
-                    L.check(lib.mi_sampler_step_small_ext_fwd(C.byref(c_), C.byref(qp), C.byref(p_), ext, stream), "mi_sampler_step_small_ext_fwd")
-                elif small:
-                    L.check(lib.mi_sampler_step_small_fwd(C.byref(c_), C.byref(qp), C.byref(p_), stream), "mi_sampler_step_small_fwd")
-                elif group and history:
-                    L.check(lib.mi_sampler_step_group_ext_fwd(C.byref(c_), C.byref(qp), C.byref(p_), ext, L.ptr(st.group_sync), stream),
-                            "mi_sampler_step_group_ext_fwd")
-                elif group:
-                    L.check(lib.mi_sampler_step_group_fwd(C.byref(c_), C.byref(qp), C.byref(p_), L.ptr(st.group_sync), stream), "mi_sampler_step_group_fwd")
-                else:
-                    L.check(lib.mi_cfg_x0_fwd(C.byref(c_), stream), "mi_cfg_x0_fwd")
-                    L.check(lib.mi_quantile_fwd(C.byref(qp), stream), "mi_quantile_fwd")
-                    if history:
-                        L.check(lib.mi_posterior_ext_fwd(C.byref(p_), ext, stream), "mi_posterior_ext_fwd")
-                    else:
-                        L.check(lib.mi_posterior_fwd(C.byref(p_), stream), "mi_posterior_fwd")
-                if advance == 0:
-                    return
-                if solver is not None:
-                    if advance == 1:
-                        L.check(lib.mi_step_advance_mapped(L.ptr(st.t_state), L.ptr(ws.times), B, ext, stream), "mi_step_advance_mapped")
-                    else:
-                        L.check(lib.mi_step_advance_by_mapped(L.ptr(st.t_state), L.ptr(ws.times), B, advance, ext, stream), "mi_step_advance_by_mapped")
-                elif advance == 1:
-                    L.check(lib.mi_step_advance(L.ptr(st.t_state), L.ptr(ws.times), B, stream), "mi_step_advance")
-                elif advance > 1:
-                    L.check(lib.mi_step_advance_by(L.ptr(st.t_state), L.ptr(ws.times), B, advance, stream), "mi_step_advance_by")
-            # several denoising steps per captured graph: one replay boundary (~9 us of idle GPU) per `per` steps instead of per step
-            cap = int(os.environ.get("MINIMAGEN_STEPS_PER_GRAPH", "5"))
-            per = next(k for k in (5, 4, 3, 2, 1) if k <= cap and T % k == 0)
-            entry = dict(step=one_step, graph=None, keep=(cp, qp, pp, tails), per=per)
-            if use_graph:
-                L.check(lib.mi_graph_begin(stream), "mi_graph_begin")
-                try:
-                    for k in range(per):
-                        if offsets:
-                            one_step(k, per if k == per - 1 else 0)
-                        else:
-                            one_step()
-                finally:
-                    g = C.c_void_p()
-                    rc = lib.mi_graph_end(stream, C.byref(g))
-                L.check(rc, "mi_graph_end")
-                entry["graph"] = g
-                if noise_dev is None:
-                    while len(cached) >= 8:                      # bounded: one exec per (guidance, threshold, shard offset) combination
-                        old = cached.pop(next(iter(cached)))
-                        # replays of the evicted exec may still be queued on a stage stream (sample() never host-syncs): drain the
-                        # device before the handle goes (rare: a 9th distinct (guidance, threshold, shard) combination)
-                        if L.backend() == "hip-gfx950":
-                            torch.cuda.synchronize(ws.dev)
-                        lib.mi_graph_destroy(old["graph"])
-                    cached[gkey] = entry
-        if use_graph:
-            try:
-                for _ in range(T // entry["per"]):
-                    L.check(lib.mi_graph_launch(entry["graph"], stream), "mi_graph_launch")
-            finally:
-                if noise_dev is not None:          # one-off graph (injected noise buffer): the exec must outlive its replays
-                    if L.backend() == "hip-gfx950":
-                        torch.cuda.current_stream().synchronize()
-                    lib.mi_graph_destroy(entry["graph"])
-        else:
-            for _ in range(T):
-                entry["step"]()
-        img = torch.empty(shape, dtype=torch.float32, device=ws.dev)
-        L.check(lib.mi_finalize_images(L.ptr(ws.x), L.ptr(img), B * n, 1 if self.auto_normalize_img else 0, stream), "mi_finalize_images")
-        if group:
-            # the grouped tail's sticky error word travels to pinned host memory behind the stage's last launch (no host synchronisation):
-            # _poll_status reads it once this call's completion event has fired
-            st.group_err_host.copy_(st.group_sync[8:12].view(torch.int32), non_blocking=True)
-            self.__dict__.setdefault("_status_stages", []).append((st, stage, (B, H, W)))
-        return img
+    def _p_sample_loop(self, unet: Unet, shape, **kw):        # Imagen.py:373-420 -> the stage's image
+        return S.p_sample_loop(self, unet, shape, group_max=SAMPLER_GROUP_MAX if SAMPLER_GROUP else 0, max_states=MAX_SOLVER_STATES, **kw)
 
     def _parse_solver(self, sample_steps, sampler, sampler_eta):
         """Per stage: None (the reference's loop on all T timesteps) or (S, sampler, eta).  Host only; raises ValueError on bad values."""
@@ -409,7 +200,7 @@ class Imagen(nn.Module):
             out.append(None if (S == T and name == 'ddpm') else (S, name, eta))
         return out
 
-    def _lowres_conditioning(self, img, image_size: int, ws, lowres_noise_level: float, noise_fn, seed, sample0, stage):
+    def _lowres_conditioning(self, unet: Unet, img, image_size: int, ws, lowres_noise_level: float, noise_fn, seed, sample0, stage):
         """Imagen.py:479-485 + :393: cubic resize (reflect pad) -> q_sample at int(T*level) -> *2-1."""
         lib = L.lib()
         stream = L.current_stream()
@@ -419,7 +210,7 @@ class Imagen(nn.Module):
         if Hin != image_size:
             # tap tables: built and uploaded once per (workspace, source size) -- an upload from pageable host memory per call would
             # block the host behind the previous call still running on this stage's stream
-            cache = ws.__dict__.setdefault("resize_tabs", {})
+            cache = ws.resize_tabs
             if (Hin, Win) not in cache:
                 _, idx_h, w_h = cubic_taps(Hin, image_size)
                 _, idx_w, w_w = cubic_taps(Win, image_size)
@@ -442,7 +233,6 @@ class Imagen(nn.Module):
         b = self.lowres_noise_schedule._host_sqrt_one_minus_alphas_cumprod[t_low]
         L.check(lib.mi_lowres_augment(L.ptr(up), L.ptr(noise), L.ptr(ws.lowres), B * n, a, b, 1 if self.auto_normalize_img else 0, stream), "mi_lowres_augment")
         ws.lowres_keepalive = (up, noise)
-        unet = [u for u in self.unets if u.engine()._ws and ws in u.engine()._ws.values()][0]
         unet.engine().prepare_lowres(ws, stream)
 
     @torch.no_grad()
@@ -571,7 +361,7 @@ class Imagen(nn.Module):
                 if unet.lowres_cond:
                     if on_gpu:
                         img.record_stream(streams[stage])
-                    self._lowres_conditioning(img, image_size, ws, lowres_sample_noise_level, _noise, _seed, _sample_offset, stage)
+                    self._lowres_conditioning(unet, img, image_size, ws, lowres_sample_noise_level, _noise, _seed, _sample_offset, stage)
                 img = self._p_sample_loop(unet, (batch_size, self.channels, image_size, image_size), noise_scheduler=noise_scheduler,
                                           ws=ws, cond_scale=cond_scale, noise_fn=_noise, seed=_seed, sample0=_sample_offset,
                                           stage=stage, use_graph=_use_graph, begun=begun.get(stage), solver=solvers[stage])
@@ -586,7 +376,7 @@ class Imagen(nn.Module):
             call_args["_revalidated"] = True
             return self.sample(**call_args)
         if self._status_stages:
-            self.__dict__.setdefault("_status_pending", []).append((prev_done, self._status_stages))
+            self._status_pending.append((prev_done, self._status_stages))
             self._status_stages = []
         if STRICT_STATUS and on_gpu and not _async:
             prev_done.synchronize()
@@ -597,16 +387,11 @@ class Imagen(nn.Module):
                 # per CALL: the event of this very call.  A later call on the OTHER lane does not wait for it -- capture it right after
                 # the call that produced the tensor (it also travels on the tensor), or use wait_pending_samples() to cover every lane
                 self.last_sample_done = prev_done
-                self.__dict__.setdefault("_lane_done", {})[lane] = prev_done
+                self._lane_done[lane] = prev_done
                 if not return_pil_images:
                     img.sample_done = prev_done
                     return img
-                caller_stream.wait_event(prev_done)          # the device -> host copy below runs on the caller's stream
-                img.record_stream(caller_stream)
-                pil = _to_pil_images(img)
-                self.check_device_status()
-                return pil
-            caller_stream.wait_event(prev_done)
+            caller_stream.wait_event(prev_done)              # (_async with PIL images: the device -> host copy below runs on the caller's stream)
             img.record_stream(caller_stream)
         if not return_pil_images:
             return img
@@ -614,56 +399,43 @@ class Imagen(nn.Module):
         self.check_device_status()
         return pil
 
+    def _poll_status(self, block: bool = False):
+        """Status of the kernels whose workgroups wait for each other (the grouped sampler tail).  Such a launch is fail-stop: when a wait
+        runs out it sets a sticky error word and turns the image -- and everything sampled from it afterwards -- into NaN.  Every sample()
+        call copies the word to pinned host memory behind its last launch; this looks at the calls whose completion event has fired
+        (``block=True``: waits for all of them) and raises MinImagenHipError for a failed one.  Called at every sample() entry, by
+        wait_pending_samples() and check_device_status().  Recovery is automatic: the stage state re-zeroes its sync buffer before its next
+        launch and keeps the separate (non-cooperative) kernels from then on."""
+        failed, rest = [], []
+        for done, stages in self._status_pending:
+            if done is not None:
+                if block:
+                    done.synchronize()
+                elif not done.query():
+                    rest.append((done, stages))
+                    continue
+            for st, stage, shape in stages:
+                err = int(st.group_err_host.item())
+                if err and not st.group_failed:
+                    st.group_failed, st.group_heal = True, True
+                    failed.append(f"stage {stage} {shape}: {err:#x}")
+                elif err:
+                    failed.append(f"stage {stage} {shape}: {err:#x} (call queued behind the failed one)")
+        self._status_pending = rest
+        if failed:
+            raise L.MinImagenHipError("grouped sampler tail: a workgroup timed out waiting for its image's other workgroups (" + "; ".join(failed) +
+                                      "); the images of that sample() call are NaN.  The stage falls back to the separate kernels from the next call on.")
 
-def _poll_status(self, block: bool = False):
-    """Status of the kernels whose workgroups wait for each other (the grouped sampler tail).  Such a launch is fail-stop: when a wait
-    runs out it sets a sticky error word and turns the image -- and everything sampled from it afterwards -- into NaN.  Every sample()
-    call copies the word to pinned host memory behind its last launch; this looks at the calls whose completion event has fired
-    (``block=True``: waits for all of them) and raises MinImagenHipError for a failed one.  Called at every sample() entry, by
-    wait_pending_samples() and check_device_status().  Recovery is automatic: the stage state re-zeroes its sync buffer before its next
-    launch and keeps the separate (non-cooperative) kernels from then on."""
-    pending = self.__dict__.get("_status_pending", [])
-    failed, rest = [], []
-    for done, stages in pending:
-        if done is not None:
-            if block:
-                done.synchronize()
-            elif not done.query():
-                rest.append((done, stages))
-                continue
-        for st, stage, shape in stages:
-            err = int(st.group_err_host.item())
-            if err and not getattr(st, "group_failed", False):
-                st.group_failed, st.group_heal = True, True
-                failed.append(f"stage {stage} {shape}: {err:#x}")
-            elif err:
-                failed.append(f"stage {stage} {shape}: {err:#x} (call queued behind the failed one)")
-    self._status_pending = rest
-    if failed:
-        raise L.MinImagenHipError("grouped sampler tail: a workgroup timed out waiting for its image's other workgroups (" + "; ".join(failed) +
-                                  "); the images of that sample() call are NaN.  The stage falls back to the separate kernels from the next call on.")
+    def check_device_status(self):
+        """Host-side check (waits for every sample() call in flight): no kernel whose workgroups wait for each other gave up waiting."""
+        self._poll_status(block=True)
 
-
-Imagen._poll_status = _poll_status
-
-
-def _check_device_status(self):
-    """Host-side check (waits for every sample() call in flight): no kernel whose workgroups wait for each other gave up waiting."""
-    self._poll_status(block=True)
-
-
-Imagen.check_device_status = _check_device_status
-
-
-def _wait_pending_samples(self, stream=None):
-    """Make ``stream`` (default: the caller's current stream) wait for the latest ``sample(_async=True)`` call of EVERY call lane; raises
-    if a call that has already completed reported a failed cooperative launch (check_device_status() waits on the host and covers all)."""
-    for ev in self.__dict__.get("_lane_done", {}).values():
-        (stream if stream is not None else torch.cuda.current_stream()).wait_event(ev)
-    self._poll_status()
-
-
-Imagen.wait_pending_samples = _wait_pending_samples
+    def wait_pending_samples(self, stream=None):
+        """Make ``stream`` (default: the caller's current stream) wait for the latest ``sample(_async=True)`` call of EVERY call lane; raises
+        if a call that has already completed reported a failed cooperative launch (check_device_status() waits on the host and covers all)."""
+        for ev in self._lane_done.values():
+            (stream if stream is not None else torch.cuda.current_stream()).wait_event(ev)
+        self._poll_status()
 
 
 def _to_pil_images(img: torch.Tensor):

@@ -11,21 +11,125 @@
 
 namespace {
 
+// ------------------------------------------------------------------ the arithmetic of one denoising step, per element
+// Written ONCE: the separate kernels (cfg_x0 / quantile_* / posterior) and the two fused tails (sampler_small / sampler_group) differ in
+// where an element lives and how the workgroups meet, never in what is computed.  Every helper is inlined into its caller.
+struct step_coef { float ca, cb, c1, c2, sigma, c5; };      // row t of the S x 8 coefficient table; c5: the multistep solvers' history term
+template <bool HISTORY>
+__device__ __forceinline__ step_coef load_step_coef(const float* coef, int t) {
+    const float* r = coef + t * 8;
+    return {r[0], r[1], r[2], r[3], r[4], HISTORY ? r[5] : 0.0f};
+}
+
+// four consecutive floats of a row of n, from element i (a multiple of 4): one 16-byte access when `vec` (n % 4 == 0), else element by
+// element inside the row (loads past the end give 0)
+__device__ __forceinline__ void ld_quad(const float* row, int i, int n, bool vec, float (&v)[4]) {
+    if (vec) { const float4 q = mi_ldg4(row + i); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
+    else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (i + e < n) ? row[i + e] : 0.0f;
+    }
+}
+__device__ __forceinline__ void st_quad(float* row, int i, int n, bool vec, const float (&v)[4]) {
+    if (vec) mi_stg4(row + i, make_float4(v[0], v[1], v[2], v[3]));
+    else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (i + e < n) row[i + e] = v[e];
+    }
+}
+
+// classifier-free guidance combine and the x0 it predicts; pred: the guided noise prediction
+__device__ __forceinline__ float guided_x0(float c, float nl, float xt, int two, float cond_scale, const step_coef& cf, float& pred) {
+    pred = c;
+    if (two) pred = __fadd_rn(nl, __fmul_rn(__fsub_rn(c, nl), cond_scale));     // Unet.py:506
+    return __fsub_rn(__fmul_rn(cf.ca, xt), __fmul_rn(cf.cb, pred));             // diffusion_model.py:159-162
+}
+
+// digit layout of a non-negative float's bit pattern (bit 31 = 0): pass 0 -> bits 30..20, pass 1 -> 19..9, pass 2 -> 8..0
+__device__ __forceinline__ int q_shift(int pass) { return pass == 0 ? 20 : (pass == 1 ? 9 : 0); }
+__device__ __forceinline__ int q_bits(int pass) { return pass == 2 ? 9 : 11; }
+
+// one element of radix pass `pass`: count its digit into lh[sel] for every selected prefix its higher digits match (pass 0 has no prefix
+// yet; `second` off: one histogram serves both order statistics)
+__device__ __forceinline__ void radix_count(unsigned (&lh)[2][MI_Q_BINS], float v, int pass, unsigned prefix0, unsigned prefix1, bool second) {
+    const int shift = q_shift(pass), nb = q_bits(pass);
+    const unsigned key = __float_as_uint(fabsf(v));
+    const unsigned hi = pass == 0 ? 0u : (key >> (shift + nb)), bin = (key >> shift) & ((1u << nb) - 1u);
+    if (hi == prefix0) atomicAdd(&lh[0][bin], 1u);
+    if (second && hi == prefix1) atomicAdd(&lh[1][bin], 1u);
+}
+
+// the dynamic threshold from the bit patterns of the two order statistics (a, bb: the statistics themselves)
+__device__ __forceinline__ float threshold_from_ranks(unsigned prefix0, unsigned prefix1, unsigned nan_count, float w, float& a, float& bb) {
+    // torch.quantile returns NaN for a row that contains a NaN (not the order statistic): NaN bit patterns sit above infinity,
+    // i.e. in the top bins of pass 0 (0x7F9.. are NaN only; arithmetic produces the canonical 0x7FC00000) -- nan_count is their sum
+    a = __uint_as_float(prefix0); bb = __uint_as_float(prefix1);
+    if (nan_count) a = bb = __uint_as_float(0x7FC00000u);
+    const float d = __fsub_rn(bb, a);
+    // ATen lerp: weight < 0.5 ? a + w*d : b - d*(1-w), multiply-add fused
+    return (fabsf(w) < 0.5f) ? fmaf(w, d, a) : fmaf(__fsub_rn(w, 1.0f), d, bb);
+}
+__device__ __forceinline__ float threshold_scale(float sq) { return (sq < 1.0f) ? 1.0f : sq; }      // Imagen.py:320 clamp_(min=1.): a NaN threshold stays NaN, as in torch
+
+// x_{t-1} of one element.  HISTORY: plus c5 * (the PREVIOUS step's thresholded x0, in pv), and pv becomes this step's for the next one
+template <bool HISTORY>
+__device__ __forceinline__ float posterior_elem(float x0, float x, float z, float s, const step_coef& cf, float& pv) {
+    const float c1 = cf.c1, c2 = cf.c2;
+    x0 = __fdiv_rn(x0 != x0 ? x0 : fminf(fmaxf(x0, -s), s), s);               // Imagen.py:323 (torch.clamp propagates NaN)
+    float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, x));                // diffusion_model.py:118-121
+    if constexpr (HISTORY) { mean = __fadd_rn(mean, __fmul_rn(cf.c5, pv)); pv = x0; }
+    return __fadd_rn(mean, __fmul_rn(cf.sigma, z));                            // Imagen.py:370
+}
+
+// ------------------------------------------------------------------ Philox4x32-10 + Box-Muller
+__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
+    const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+    const unsigned hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
+    const unsigned hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+    const unsigned n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
+    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+}
+__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+// four N(0,1) draws for (seed, sample, stream, quad index)
+__device__ __forceinline__ void randn4(unsigned long long seed, unsigned sample, unsigned stream, unsigned quad, float (&z)[4]) {
+    unsigned c[4] = {quad, sample, stream, 0x4D494E49u};
+    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+    const float u0 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float u1 = ((float)(c[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float u2 = ((float)(c[2] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float u3 = ((float)(c[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
+    const float a0 = 6.28318530717958647692f * u1, a1 = 6.28318530717958647692f * u3;
+    z[0] = r0 * cosf(a0); z[1] = r0 * sinf(a0);
+    z[2] = r1 * cosf(a1); z[3] = r1 * sinf(a1);
+}
+
+// the draws of step k (counted from the first step) for quad qd of image b: the injected buffer [T][B][n], or Philox
+__device__ __forceinline__ void step_noise4(const mi_posterior_params& pp, int b, int k, int qd, int n, bool vec, float (&z)[4]) {
+    if (pp.noise) ld_quad(pp.noise + ((size_t)k * pp.B + b) * n, 4 * qd, n, vec, z);
+    else randn4(pp.seed_dev ? *pp.seed_dev : pp.seed, (unsigned)(pp.sample0 + b), (unsigned)(pp.stream_base + k), (unsigned)qd, z);
+}
+
 // ------------------------------------------------------------------ K11 epilogue
 template <bool HIST>
 __global__ __launch_bounds__(256) void cfg_x0_kernel(const mi_cfg_x0_params p) {
     __shared__ unsigned lh[HIST ? MI_Q_BINS : 1];      // pass 0 of the radix select (bits 30..20 of |x0|), fused into the producer of x0
     const int b = blockIdx.y;
     const int t = p.t_state ? *p.t_state - p.t_off : 0;
-    const float ca = p.coef ? p.coef[t * 8 + 0] : 0.0f, cb = p.coef ? p.coef[t * 8 + 1] : 0.0f;
+    const step_coef cf = p.coef ? load_step_coef<false>(p.coef, t) : step_coef{};
     if constexpr (HIST) {
         for (int i = threadIdx.x; i < MI_Q_BINS; i += 256) lh[i] = 0u;
         __syncthreads();
     }
     auto one = [&](float c, float nl, float xt, float& pred, float& x0) {
-        pred = c;
-        if (p.two) pred = __fadd_rn(nl, __fmul_rn(__fsub_rn(c, nl), p.cond_scale));     // Unet.py:506
-        x0 = __fsub_rn(__fmul_rn(ca, xt), __fmul_rn(cb, pred));                          // diffusion_model.py:159-162
+        x0 = guided_x0(c, nl, xt, p.two, p.cond_scale, cf, pred);
         if constexpr (HIST) { if (p.x0) atomicAdd(&lh[__float_as_uint(fabsf(x0)) >> 20], 1u); }
     };
     if ((p.n & 3) == 0) {                           // 16-byte accesses (every image size the cascade uses)
@@ -62,10 +166,6 @@ __global__ __launch_bounds__(256) void cfg_x0_kernel(const mi_cfg_x0_params p) {
 }
 
 // ------------------------------------------------------------------ K12 radix select
-// digit layout of a non-negative float's bit pattern (bit 31 = 0): pass 0 -> bits 30..20, pass 1 -> 19..9, pass 2 -> 8..0
-__device__ __forceinline__ int q_shift(int pass) { return pass == 0 ? 20 : (pass == 1 ? 9 : 0); }
-__device__ __forceinline__ int q_bits(int pass) { return pass == 2 ? 9 : 11; }
-
 // Block-wide: locate the bin of `hist` (MI_Q_BINS entries) that holds 0-based rank r; returns bin and the
 // rank inside the bin.  All 256 work-items call it; result broadcast through LDS.
 __device__ void q_find_bin(const unsigned* hist, unsigned r, int* sh_scratch, unsigned& bin_out, unsigned& r_out, bool active = true) {
@@ -119,16 +219,8 @@ __global__ __launch_bounds__(256) void quantile_hist_kernel(const mi_quantile_pa
     }
     for (int i = tid; i < 2 * MI_Q_BINS; i += 256) (&lh[0][0])[i] = 0u;
     __syncthreads();
-    const int shift = q_shift(PASS), nb = q_bits(PASS);
-    const unsigned mask = (1u << nb) - 1u;
     const float* xb = p.x0 + (size_t)b * p.n;
-    auto count = [&](float v) {
-        const unsigned key = __float_as_uint(fabsf(v));
-        const unsigned hi = PASS == 0 ? 0u : (key >> (shift + nb));
-        const unsigned bin = (key >> shift) & mask;
-        if (hi == prefix[0]) atomicAdd(&lh[0][bin], 1u);
-        if (PASS > 0 && hi == prefix[1]) atomicAdd(&lh[1][bin], 1u);              // pass 0: one histogram serves both order statistics
-    };
+    auto count = [&](float v) { radix_count(lh, v, PASS, prefix[0], prefix[1], PASS > 0); };      // pass 0: one histogram serves both order statistics
     if ((p.n & 3) == 0) {
         for (int q = blockIdx.x * 256 + tid; q < (p.n >> 2); q += gridDim.x * 256) {
             const float4 v = mi_ldg4(xb + 4 * q);
@@ -160,17 +252,11 @@ __global__ __launch_bounds__(256) void quantile_finish_kernel(const mi_quantile_
         }
     }
     if (threadIdx.x == 0) {
-        // torch.quantile returns NaN for a row that contains a NaN (not the order statistic): NaN bit patterns sit above infinity,
-        // i.e. in the top bins of pass 0 (0x7F9.. are NaN only; arithmetic produces the canonical 0x7FC00000)
         const unsigned* h0 = p.hist + ((size_t)b * 2) * MI_Q_BINS;
         unsigned nan_count = 0;
-        for (int k = 0x7F9; k < MI_Q_BINS; ++k) nan_count += h0[k];
-        float a = __uint_as_float(prefix[0]), bb = __uint_as_float(prefix[1]);
-        if (nan_count) a = bb = __uint_as_float(0x7FC00000u);
-        const float d = __fsub_rn(bb, a);
-        // ATen lerp: weight < 0.5 ? a + w*d : b - d*(1-w), multiply-add fused
-        const float s = (fabsf(p.w) < 0.5f) ? fmaf(p.w, d, a) : fmaf(__fsub_rn(p.w, 1.0f), d, bb);
-        p.s_out[b] = s;
+        for (int k = 0x7F9; k < MI_Q_BINS; ++k) nan_count += h0[k];          // the NaN bins of pass 0 (threshold_from_ranks)
+        float a, bb;
+        p.s_out[b] = threshold_from_ranks(prefix[0], prefix[1], nan_count, p.w, a, bb);
         if (p.v_out) { p.v_out[2 * b] = a; p.v_out[2 * b + 1] = bb; }
     }
     if (p.self_cleaning) {       // leave this image's counters zeroed for the next denoising step (no memset launch)
@@ -180,36 +266,6 @@ __global__ __launch_bounds__(256) void quantile_finish_kernel(const mi_quantile_
             for (int i = threadIdx.x; i < 2 * MI_Q_BINS; i += 256) gh[i] = 0u;
         }
     }
-}
-
-// ------------------------------------------------------------------ Philox4x32-10 + Box-Muller
-__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
-    const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-    const unsigned hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-    const unsigned hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-    const unsigned n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-// four N(0,1) draws for (seed, sample, stream, quad index)
-__device__ __forceinline__ void randn4(unsigned long long seed, unsigned sample, unsigned stream, unsigned quad, float (&z)[4]) {
-    unsigned c[4] = {quad, sample, stream, 0x4D494E49u};
-    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
-    const float u0 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u1 = ((float)(c[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c[2] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u3 = ((float)(c[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
-    const float a0 = 6.28318530717958647692f * u1, a1 = 6.28318530717958647692f * u3;
-    z[0] = r0 * cosf(a0); z[1] = r0 * sinf(a0);
-    z[2] = r1 * cosf(a1); z[3] = r1 * sinf(a1);
 }
 
 __global__ __launch_bounds__(256) void randn_fill_kernel(float* out, int n, unsigned long long seed, int sample0, int stream_id) {
@@ -236,52 +292,23 @@ __global__ __launch_bounds__(256) void posterior_kernel(const mi_posterior_param
     static_assert(sizeof...(EXT) == (HISTORY ? 1 : 0), "the history kernels take mi_sampler_ext_params");
     const int b = blockIdx.y;
     const int t = *p.t_state - p.t_off;
-    const float c1 = p.coef[t * 8 + 2], c2 = p.coef[t * 8 + 3], sigma = p.coef[t * 8 + 4];
-    const float c5 = HISTORY ? p.coef[t * 8 + 5] : 0.0f;
+    const step_coef cf = load_step_coef<HISTORY>(p.coef, t);
     float* const prev = x0_prev_of(ext...);
-    const float sq = p.s_q[b];
-    const float s = (sq < 1.0f) ? 1.0f : sq;                                     // Imagen.py:320 clamp_(min=1.): a NaN threshold stays NaN, as in torch
+    const float s = threshold_scale(p.s_q[b]);
     const int k = (p.T - 1) - t;
-    const float* nz = p.noise ? p.noise + ((size_t)k * p.B + b) * p.n : nullptr;
-    const int nq = (p.n + 3) / 4;
-    const bool vec = (p.n & 3) == 0;
-    auto one = [&](float x0, float x, float z, float& pv) {
-        x0 = __fdiv_rn(x0 != x0 ? x0 : fminf(fmaxf(x0, -s), s), s);               // Imagen.py:323 (torch.clamp propagates NaN)
-        float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, x));                // diffusion_model.py:118-121
-        if constexpr (HISTORY) { mean = __fadd_rn(mean, __fmul_rn(c5, pv)); pv = x0; }
-        return __fadd_rn(mean, __fmul_rn(sigma, z));                               // Imagen.py:370
-    };
+    const int n = p.n, nq = (n + 3) / 4;
+    const bool vec = (n & 3) == 0;
+    const size_t ob = (size_t)b * n;
     for (int qd = blockIdx.x * 256 + threadIdx.x; qd < nq; qd += gridDim.x * 256) {
-        float z[4];
-        if (nz) {
-            if (vec) { const float4 v = mi_ldg4(nz + 4 * qd); z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w; }
-            else {
+        float z[4], x0[4], x[4], pv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        step_noise4(p, b, k, qd, n, vec, z);
+        ld_quad(p.x0 + ob, 4 * qd, n, vec, x0);
+        ld_quad(p.x + ob, 4 * qd, n, vec, x);
+        if constexpr (HISTORY) ld_quad(prev + ob, 4 * qd, n, vec, pv);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) z[e] = (4 * qd + e < p.n) ? nz[4 * qd + e] : 0.0f;
-            }
-        } else {
-            randn4(p.seed_dev ? *p.seed_dev : p.seed, (unsigned)(p.sample0 + b), (unsigned)(p.stream_base + k), (unsigned)qd, z);
-        }
-        if (vec) {
-            const size_t o = (size_t)b * p.n + 4 * qd;
-            const float4 x0 = mi_ldg4(p.x0 + o), x = mi_ldg4(p.x + o);
-            float4 pv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if constexpr (HISTORY) pv = mi_ldg4(prev + o);
-            mi_stg4(p.x + o, make_float4(one(x0.x, x.x, z[0], pv.x), one(x0.y, x.y, z[1], pv.y), one(x0.z, x.z, z[2], pv.z), one(x0.w, x.w, z[3], pv.w)));
-            if constexpr (HISTORY) mi_stg4(prev + o, pv);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int i = 4 * qd + e;
-                if (i < p.n) {
-                    const size_t o = (size_t)b * p.n + i;
-                    float pv = 0.0f;
-                    if constexpr (HISTORY) pv = prev[o];
-                    p.x[o] = one(p.x0[o], p.x[o], z[e], pv);
-                    if constexpr (HISTORY) prev[o] = pv;
-                }
-            }
-        }
+        for (int e = 0; e < 4; ++e) x[e] = posterior_elem<HISTORY>(x0[e], x[e], z[e], s, cf, pv[e]);      // (past the row's end: on zeros, not stored)
+        st_quad(p.x + ob, 4 * qd, n, vec, x);
+        if constexpr (HISTORY) st_quad(prev + ob, 4 * qd, n, vec, pv);
     }
 }
 
@@ -300,9 +327,7 @@ __global__ __launch_bounds__(SS_NT) void sampler_small_kernel(const mi_cfg_x0_pa
     __shared__ unsigned nan_sh;
     const int tid = threadIdx.x, b = blockIdx.x, n = c.n, nq = (n + 3) / 4;
     const int t = *c.t_state - c.t_off;
-    const float ca = c.coef[t * 8 + 0], cb = c.coef[t * 8 + 1];
-    const float c1 = c.coef[t * 8 + 2], c2 = c.coef[t * 8 + 3], sigma = c.coef[t * 8 + 4];
-    const float c5 = HISTORY ? c.coef[t * 8 + 5] : 0.0f;
+    const step_coef cf = load_step_coef<HISTORY>(c.coef, t);
     float* const prev = x0_prev_of(ext...);
     const bool vec = (n & 3) == 0;
     const size_t ob = (size_t)b * n, on = (size_t)(b + c.B) * n;
@@ -313,36 +338,27 @@ __global__ __launch_bounds__(SS_NT) void sampler_small_kernel(const mi_cfg_x0_pa
 #pragma unroll
     for (int u = 0; u < SS_MAXQ; ++u) {
         const int qd = tid + u * SS_NT;
-        float cc[4], nl[4], pr[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { cc[e] = nl[e] = xtv[u][e] = x0v[u][e] = 0.0f; }
+        for (int e = 0; e < 4; ++e) xtv[u][e] = x0v[u][e] = 0.0f;
         if (qd < nq) {
-            if (vec) {
-                const float4 a = mi_ldg4(c.pred2 + ob + 4 * qd), xx = mi_ldg4(c.x_t + ob + 4 * qd);
-                const float4 d = c.two ? mi_ldg4(c.pred2 + on + 4 * qd) : a;
-                cc[0] = a.x; cc[1] = a.y; cc[2] = a.z; cc[3] = a.w; nl[0] = d.x; nl[1] = d.y; nl[2] = d.z; nl[3] = d.w;
-                xtv[u][0] = xx.x; xtv[u][1] = xx.y; xtv[u][2] = xx.z; xtv[u][3] = xx.w;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (4 * qd + e < n) { cc[e] = c.pred2[ob + 4 * qd + e]; nl[e] = c.two ? c.pred2[on + 4 * qd + e] : cc[e]; xtv[u][e] = c.x_t[ob + 4 * qd + e]; }
-            }
+            float cc[4], nl[4], pr;
+            ld_quad(c.pred2 + ob, 4 * qd, n, vec, cc);
+            ld_quad(c.x_t + ob, 4 * qd, n, vec, xtv[u]);
+            if (c.two) ld_quad(c.pred2 + on, 4 * qd, n, vec, nl);
+            else { nl[0] = cc[0]; nl[1] = cc[1]; nl[2] = cc[2]; nl[3] = cc[3]; }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                pr[e] = cc[e];
-                if (c.two) pr[e] = __fadd_rn(nl[e], __fmul_rn(__fsub_rn(cc[e], nl[e]), c.cond_scale));       // Unet.py:506
-                x0v[u][e] = __fsub_rn(__fmul_rn(ca, xtv[u][e]), __fmul_rn(cb, pr[e]));                      // diffusion_model.py:159-162
+                x0v[u][e] = guided_x0(cc[e], nl[e], xtv[u][e], c.two, c.cond_scale, cf, pr);
                 if (4 * qd + e < n) {
                     atomicAdd(&lh[0][__float_as_uint(fabsf(x0v[u][e])) >> 20], 1u);
-                    if (c.pred_out) c.pred_out[ob + 4 * qd + e] = pr[e];
+                    if (c.pred_out) c.pred_out[ob + 4 * qd + e] = pr;
                     if (c.x0) c.x0[ob + 4 * qd + e] = x0v[u][e];
                 }
             }
         }
     }
     __syncthreads();
-    // torch.quantile returns NaN for a row that contains a NaN: NaN patterns sit in the top bins of pass 0 (as quantile_finish_kernel)
-    if (tid < MI_Q_BINS - 0x7F9) { const unsigned v = lh[0][0x7F9 + tid]; if (v) atomicAdd(&nan_sh, v); }
+    if (tid < MI_Q_BINS - 0x7F9) { const unsigned v = lh[0][0x7F9 + tid]; if (v) atomicAdd(&nan_sh, v); }      // the NaN bins of pass 0 (threshold_from_ranks)
     unsigned prefix[2] = {0u, 0u}, rk[2] = {(unsigned)q.k_lo, (unsigned)q.k_hi};
 #pragma unroll
     for (int ps = 0; ps < 3; ++ps) {
@@ -351,20 +367,11 @@ __global__ __launch_bounds__(SS_NT) void sampler_small_kernel(const mi_cfg_x0_pa
             __syncthreads();
             for (int i = tid; i < 2 * MI_Q_BINS; i += SS_NT) (&lh[0][0])[i] = 0u;
             __syncthreads();
-            const int shift = q_shift(ps), nb = q_bits(ps);
-            const unsigned mask = (1u << nb) - 1u;
 #pragma unroll
             for (int u = 0; u < SS_MAXQ; ++u)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int i = 4 * (tid + u * SS_NT) + e;
-                    if (i < n) {
-                        const unsigned key = __float_as_uint(fabsf(x0v[u][e]));
-                        const unsigned hi = key >> (shift + nb), bin = (key >> shift) & mask;
-                        if (hi == prefix[0]) atomicAdd(&lh[0][bin], 1u);
-                        if (hi == prefix[1]) atomicAdd(&lh[1][bin], 1u);
-                    }
-                }
+                for (int e = 0; e < 4; ++e)
+                    if (4 * (tid + u * SS_NT) + e < n) radix_count(lh, x0v[u][e], ps, prefix[0], prefix[1], true);
             __syncthreads();
         }
 #pragma unroll
@@ -375,71 +382,37 @@ __global__ __launch_bounds__(SS_NT) void sampler_small_kernel(const mi_cfg_x0_pa
             rk[sel] = rr;
         }
     }
-    float a = __uint_as_float(prefix[0]), bb = __uint_as_float(prefix[1]);
-    if (nan_sh) a = bb = __uint_as_float(0x7FC00000u);
-    const float d = __fsub_rn(bb, a);
-    const float sq = (fabsf(q.w) < 0.5f) ? fmaf(q.w, d, a) : fmaf(__fsub_rn(q.w, 1.0f), d, bb);      // ATen lerp (fused multiply-add)
+    float a, bb;
+    const float sq = threshold_from_ranks(prefix[0], prefix[1], nan_sh, q.w, a, bb);
     if (tid == 0) {
         if (q.s_out) q.s_out[b] = sq;
         if (q.v_out) { q.v_out[2 * b] = a; q.v_out[2 * b + 1] = bb; }
     }
-    const float s = (sq < 1.0f) ? 1.0f : sq;                                     // Imagen.py:320 clamp_(min=1.): a NaN threshold stays NaN
+    const float s = threshold_scale(sq);
     const int k = (pp.T - 1) - t;
-    const float* nz = pp.noise ? pp.noise + ((size_t)k * pp.B + b) * n : nullptr;
 #pragma unroll
     for (int u = 0; u < SS_MAXQ; ++u) {
         const int qd = tid + u * SS_NT;
         if (qd >= nq) continue;
-        float z[4];
-        if (nz) {
+        float z[4], r[4], pv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        step_noise4(pp, b, k, qd, n, vec, z);
+        if constexpr (HISTORY) ld_quad(prev + ob, 4 * qd, n, vec, pv);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) z[e] = (4 * qd + e < n) ? nz[4 * qd + e] : 0.0f;
-        } else {
-            randn4(pp.seed_dev ? *pp.seed_dev : pp.seed, (unsigned)(pp.sample0 + b), (unsigned)(pp.stream_base + k), (unsigned)qd, z);
-        }
-        float r[4], pv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (HISTORY) {
-            if (vec) { const float4 v = mi_ldg4(prev + ob + 4 * qd); pv[0] = v.x; pv[1] = v.y; pv[2] = v.z; pv[3] = v.w; }
-            else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (4 * qd + e < n) pv[e] = prev[ob + 4 * qd + e];
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float x0 = x0v[u][e];
-            x0 = __fdiv_rn(x0 != x0 ? x0 : fminf(fmaxf(x0, -s), s), s);                  // Imagen.py:323 (torch.clamp propagates NaN)
-            float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, xtv[u][e]));           // diffusion_model.py:118-121
-            if constexpr (HISTORY) { mean = __fadd_rn(mean, __fmul_rn(c5, pv[e])); pv[e] = x0; }
-            r[e] = __fadd_rn(mean, __fmul_rn(sigma, z[e]));                               // Imagen.py:370
-        }
-        if (vec) {
-            mi_stg4(pp.x + ob + 4 * qd, make_float4(r[0], r[1], r[2], r[3]));
-            if constexpr (HISTORY) mi_stg4(prev + ob + 4 * qd, make_float4(pv[0], pv[1], pv[2], pv[3]));
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) if (4 * qd + e < n) {
-                pp.x[ob + 4 * qd + e] = r[e];
-                if constexpr (HISTORY) prev[ob + 4 * qd + e] = pv[e];
-            }
-        }
+        for (int e = 0; e < 4; ++e) r[e] = posterior_elem<HISTORY>(x0v[u][e], xtv[u][e], z[e], s, cf, pv[e]);
+        st_quad(pp.x + ob, 4 * qd, n, vec, r);
+        if constexpr (HISTORY) st_quad(prev + ob, 4 * qd, n, vec, pv);
     }
 }
 
-__global__ void step_advance_kernel(int* t_state, long long* times, int B, int set, int value) {
-    const int t = set == 1 ? value : (*t_state - (set == 2 ? value : 1));
-    __syncthreads();
-    for (int b = threadIdx.x; b < B; b += blockDim.x) times[b] = (long long)t;
-    if (threadIdx.x == 0) *t_state = t;
-}
-
-// the same with a step -> trained-timestep map: *t_state stays the STEP index k (what the coefficient table, the step tables and the noise
-// are indexed by), the U-Net's conditioning sees times[b] = t_map[k].  Past the last step (k < 0: the advance behind step 0) times keep
-// t_map[0]; nothing reads them before the next mi_step_set_mapped.
-__global__ void step_advance_mapped_kernel(int* t_state, long long* times, int B, int set, int value, const int* t_map) {
+// set (set == 1) or advance (by value when set == 2, else by 1) the device-resident step and the timestep the U-Net's conditioning sees.
+// MAPPED, a step -> trained-timestep map: *t_state stays the STEP index k (what the coefficient table, the step tables and the noise
+// are indexed by), times[b] = t_map[k].  Past the last step (k < 0: the advance behind step 0) times keep t_map[0]; nothing reads them
+// before the next mi_step_set_mapped.
+template <bool MAPPED>
+__global__ void step_advance_kernel(int* t_state, long long* times, int B, int set, int value, const int* t_map) {
     const int k = set == 1 ? value : (*t_state - (set == 2 ? value : 1));
     __syncthreads();
-    const long long t = (long long)t_map[k < 0 ? 0 : k];
+    const long long t = MAPPED ? (long long)t_map[k < 0 ? 0 : k] : (long long)k;
     for (int b = threadIdx.x; b < B; b += blockDim.x) times[b] = t;
     if (threadIdx.x == 0) *t_state = k;
 }
@@ -551,9 +524,7 @@ __global__ __launch_bounds__(SG_NT) void sampler_group_kernel(const mi_cfg_x0_pa
     for (int i = g * SG_NT + tid; i < 5 * MI_Q_BINS / 4; i += G * SG_NT) mi_buf_store_f32x4_sc1(zbuf, (unsigned)i * 16u, (f32x4){0.f, 0.f, 0.f, 0.f});
 
     const int t = *c.t_state - c.t_off;
-    const float ca = c.coef[t * 8 + 0], cb = c.coef[t * 8 + 1];
-    const float c1 = c.coef[t * 8 + 2], c2 = c.coef[t * 8 + 3], sigma = c.coef[t * 8 + 4];
-    const float c5 = HISTORY ? c.coef[t * 8 + 5] : 0.0f;
+    const step_coef cf = load_step_coef<HISTORY>(c.coef, t);
     float* const prev = x0_prev_of(ext...);
     const size_t ob = (size_t)b * n, on = (size_t)(b + c.B) * n;
     const int q0 = g * SG_NT * SG_MAXQ;                        // this workgroup's quads: q0 + tid + u * SG_NT
@@ -570,19 +541,17 @@ __global__ __launch_bounds__(SG_NT) void sampler_group_kernel(const mi_cfg_x0_pa
 #pragma unroll
     for (int u = 0; u < SG_MAXQ; ++u) {
         const int qd = q0 + tid + u * SG_NT;
-        float cc[4], nl[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { cc[e] = nl[e] = xtv[u][e] = x0v[u][e] = 0.0f; }
+        for (int e = 0; e < 4; ++e) xtv[u][e] = x0v[u][e] = 0.0f;
         if (qd < nq) {
-            const float4 a = mi_ldg4(c.pred2 + ob + 4 * qd), xx = mi_ldg4(c.x_t + ob + 4 * qd);
-            const float4 d = c.two ? mi_ldg4(c.pred2 + on + 4 * qd) : a;
-            cc[0] = a.x; cc[1] = a.y; cc[2] = a.z; cc[3] = a.w; nl[0] = d.x; nl[1] = d.y; nl[2] = d.z; nl[3] = d.w;
-            xtv[u][0] = xx.x; xtv[u][1] = xx.y; xtv[u][2] = xx.z; xtv[u][3] = xx.w;
+            float cc[4], nl[4], pr;
+            ld_quad(c.pred2 + ob, 4 * qd, n, true, cc);
+            ld_quad(c.x_t + ob, 4 * qd, n, true, xtv[u]);
+            if (c.two) ld_quad(c.pred2 + on, 4 * qd, n, true, nl);
+            else { nl[0] = cc[0]; nl[1] = cc[1]; nl[2] = cc[2]; nl[3] = cc[3]; }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float pr = cc[e];
-                if (c.two) pr = __fadd_rn(nl[e], __fmul_rn(__fsub_rn(cc[e], nl[e]), c.cond_scale));       // Unet.py:506
-                x0v[u][e] = __fsub_rn(__fmul_rn(ca, xtv[u][e]), __fmul_rn(cb, pr));                       // diffusion_model.py:159-162
+                x0v[u][e] = guided_x0(cc[e], nl[e], xtv[u][e], c.two, c.cond_scale, cf, pr);
                 atomicAdd(&lh[0][__float_as_uint(fabsf(x0v[u][e])) >> 20], 1u);
                 if (c.pred_out) c.pred_out[ob + 4 * qd + e] = pr;
                 if (c.x0) c.x0[ob + 4 * qd + e] = x0v[u][e];
@@ -632,20 +601,12 @@ __global__ __launch_bounds__(SG_NT) void sampler_group_kernel(const mi_cfg_x0_pa
             __syncthreads();
             for (int i = tid; i < 2 * MI_Q_BINS; i += SG_NT) (&lh[0][0])[i] = 0u;
             __syncthreads();
-            const int shift = q_shift(ps), nb = q_bits(ps);
-            const unsigned mask = (1u << nb) - 1u;
             one = prefix[0] == prefix[1];          // both ranks in one bin so far (the usual case: neighbours): one histogram serves both
 #pragma unroll
             for (int u = 0; u < SG_MAXQ; ++u)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (q0 + tid + u * SG_NT < nq) {
-                        const unsigned key = __float_as_uint(fabsf(x0v[u][e]));
-                        const unsigned hi = key >> (shift + nb), bin = (key >> shift) & mask;
-                        if (hi == prefix[0]) atomicAdd(&lh[0][bin], 1u);
-                        if (!one && hi == prefix[1]) atomicAdd(&lh[1][bin], 1u);
-                    }
-                }
+                for (int e = 0; e < 4; ++e)
+                    if (q0 + tid + u * SG_NT < nq) radix_count(lh, x0v[u][e], ps, prefix[0], prefix[1], !one);
             if (!exchange(ps, 2 * ps - 1, one ? 1 : 2)) { poison(); return; }
         }
 #pragma unroll
@@ -656,36 +617,25 @@ __global__ __launch_bounds__(SG_NT) void sampler_group_kernel(const mi_cfg_x0_pa
             rk[sel] = rr;
         }
     }
-    float a = __uint_as_float(prefix[0]), bb = __uint_as_float(prefix[1]);
-    if (nan_sh) a = bb = __uint_as_float(0x7FC00000u);
-    const float d = __fsub_rn(bb, a);
-    const float sq = (fabsf(q.w) < 0.5f) ? fmaf(q.w, d, a) : fmaf(__fsub_rn(q.w, 1.0f), d, bb);      // ATen lerp (fused multiply-add)
+    float a, bb;
+    const float sq = threshold_from_ranks(prefix[0], prefix[1], nan_sh, q.w, a, bb);
     if (tid == 0 && g == 0) {
         if (q.s_out) q.s_out[b] = sq;
         if (q.v_out) { q.v_out[2 * b] = a; q.v_out[2 * b + 1] = bb; }
     }
-    const float s = (sq < 1.0f) ? 1.0f : sq;                                     // Imagen.py:320 clamp_(min=1.): a NaN threshold stays NaN
+    const float s = threshold_scale(sq);
     const int k = (pp.T - 1) - t;
-    const float* nz = pp.noise ? pp.noise + ((size_t)k * pp.B + b) * n : nullptr;
 #pragma unroll
     for (int u = 0; u < SG_MAXQ; ++u) {
         const int qd = q0 + tid + u * SG_NT;
         if (qd >= nq) continue;
-        float z[4];
-        if (nz) { const float4 v = mi_ldg4(nz + 4 * qd); z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w; }
-        else randn4(pp.seed_dev ? *pp.seed_dev : pp.seed, (unsigned)(pp.sample0 + b), (unsigned)(pp.stream_base + k), (unsigned)qd, z);
-        float r[4], pv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (HISTORY) { const float4 v = mi_ldg4(prev + ob + 4 * qd); pv[0] = v.x; pv[1] = v.y; pv[2] = v.z; pv[3] = v.w; }
+        float z[4], r[4], pv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        step_noise4(pp, b, k, qd, n, true, z);
+        if constexpr (HISTORY) ld_quad(prev + ob, 4 * qd, n, true, pv);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float x0 = x0v[u][e];
-            x0 = __fdiv_rn(x0 != x0 ? x0 : fminf(fmaxf(x0, -s), s), s);                  // Imagen.py:323 (torch.clamp propagates NaN)
-            float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, xtv[u][e]));           // diffusion_model.py:118-121
-            if constexpr (HISTORY) { mean = __fadd_rn(mean, __fmul_rn(c5, pv[e])); pv[e] = x0; }
-            r[e] = __fadd_rn(mean, __fmul_rn(sigma, z[e]));                               // Imagen.py:370
-        }
-        mi_stg4(pp.x + ob + 4 * qd, make_float4(r[0], r[1], r[2], r[3]));
-        if constexpr (HISTORY) mi_stg4(prev + ob + 4 * qd, make_float4(pv[0], pv[1], pv[2], pv[3]));
+        for (int e = 0; e < 4; ++e) r[e] = posterior_elem<HISTORY>(x0v[u][e], xtv[u][e], z[e], s, cf, pv[e]);
+        st_quad(pp.x + ob, 4 * qd, n, true, r);
+        if constexpr (HISTORY) st_quad(prev + ob, 4 * qd, n, true, pv);
     }
 }
 
@@ -713,13 +663,19 @@ extern "C" int mi_quantile_fwd(const mi_quantile_params* p, void* stream) {
     return mi_check_launch("quantile kernels");
 }
 
-static int sampler_step_small(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* stream) {
-    if (c->B <= 0 || c->n <= 0 || q->B != c->B || pp->B != c->B || q->n != c->n || pp->n != c->n) { mi_set_error("mi_sampler_step_small_fwd: inconsistent B / n"); return MI_ERR_INVALID; }
-    if (c->n > MI_SAMPLER_SMALL_N) { mi_set_error("mi_sampler_step_small_fwd: n = %d > %d", c->n, MI_SAMPLER_SMALL_N); return MI_ERR_UNSUPPORTED; }
+// what the two fused tails ask of their three parameter blocks (the blocks of the separate kernels, describing ONE step)
+static int check_step_params(const char* name, const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp) {
+    if (c->B <= 0 || c->n <= 0 || q->B != c->B || pp->B != c->B || q->n != c->n || pp->n != c->n) { mi_set_error("%s: inconsistent B / n", name); return MI_ERR_INVALID; }
     if (!c->x_t || !c->coef || !c->t_state || !pp->x || c->t_state != pp->t_state || c->t_off != pp->t_off || c->coef != pp->coef || c->x_t != pp->x) {
-        mi_set_error("mi_sampler_step_small_fwd: needs x_t == x, one coef table and one t_state / t_off for the step"); return MI_ERR_INVALID;
+        mi_set_error("%s: needs x_t == x, one coef table and one t_state / t_off for the step", name); return MI_ERR_INVALID;
     }
-    if (q->k_lo < 0 || q->k_hi >= q->n || q->k_lo > q->k_hi) { mi_set_error("mi_sampler_step_small_fwd: bad ranks"); return MI_ERR_INVALID; }
+    if (q->k_lo < 0 || q->k_hi >= q->n || q->k_lo > q->k_hi) { mi_set_error("%s: bad ranks", name); return MI_ERR_INVALID; }
+    return MI_OK;
+}
+
+static int sampler_step_small(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* stream) {
+    if (const int rc = check_step_params("mi_sampler_step_small_fwd", c, q, pp)) return rc;
+    if (c->n > MI_SAMPLER_SMALL_N) { mi_set_error("mi_sampler_step_small_fwd: n = %d > %d", c->n, MI_SAMPLER_SMALL_N); return MI_ERR_UNSUPPORTED; }
     if (e) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_small_kernel<true, mi_sampler_ext_params>), dim3(c->B), dim3(SS_NT), 0, (hipStream_t)stream, *c, *q, *pp, *e);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_small_kernel<false>), dim3(c->B), dim3(SS_NT), 0, (hipStream_t)stream, *c, *q, *pp);
     return mi_check_launch("sampler_small_kernel");
@@ -741,14 +697,10 @@ extern "C" long long mi_sampler_group_sync_bytes(int B, int n) {
     return (B > 0 && mi_sampler_group_size(n) > 0) ? sg_sync_layout(B).total : 0;
 }
 static int sampler_step_group(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* sync, void* stream) {
-    if (c->B <= 0 || c->n <= 0 || q->B != c->B || pp->B != c->B || q->n != c->n || pp->n != c->n) { mi_set_error("mi_sampler_step_group_fwd: inconsistent B / n"); return MI_ERR_INVALID; }
+    if (const int rc = check_step_params("mi_sampler_step_group_fwd", c, q, pp)) return rc;
     const int G = mi_sampler_group_size(c->n);
     if (!G) { mi_set_error("mi_sampler_step_group_fwd: n = %d unsupported (a multiple of 4, at most %d)", c->n, 256 * SG_NT * SG_MAXQ * 4); return MI_ERR_UNSUPPORTED; }
     if (!sync) { mi_set_error("mi_sampler_step_group_fwd: sync buffer missing"); return MI_ERR_INVALID; }
-    if (!c->x_t || !c->coef || !c->t_state || !pp->x || c->t_state != pp->t_state || c->t_off != pp->t_off || c->coef != pp->coef || c->x_t != pp->x) {
-        mi_set_error("mi_sampler_step_group_fwd: needs x_t == x, one coef table and one t_state / t_off for the step"); return MI_ERR_INVALID;
-    }
-    if (q->k_lo < 0 || q->k_hi >= q->n || q->k_lo > q->k_hi) { mi_set_error("mi_sampler_step_group_fwd: bad ranks"); return MI_ERR_INVALID; }
     if (e) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_group_kernel<true, mi_sampler_ext_params>), dim3(c->B * G), dim3(SG_NT), 0, (hipStream_t)stream, *c, *q, *pp, (char*)sync, G, *e);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_group_kernel<false>), dim3(c->B * G), dim3(SG_NT), 0, (hipStream_t)stream, *c, *q, *pp, (char*)sync, G);
     return mi_check_launch("sampler_group_kernel");
@@ -760,46 +712,46 @@ extern "C" int mi_sampler_step_group_ext_fwd(const mi_cfg_x0_params* c, const mi
     return sampler_step_group(c, q, pp, (e && e->x0_prev) ? e : nullptr, sync, stream);
 }
 
-extern "C" int mi_posterior_fwd(const mi_posterior_params* p, void* stream) {
-    if (p->B <= 0 || p->n <= 0) { mi_set_error("mi_posterior_fwd: empty"); return MI_ERR_INVALID; }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(posterior_kernel<false>), dim3(grid_for((p->n + 3) / 4, 256), p->B), dim3(256), 0, (hipStream_t)stream, *p);
+static int posterior_step(const char* name, const mi_posterior_params* p, const mi_sampler_ext_params* e, void* stream) {
+    if (p->B <= 0 || p->n <= 0) { mi_set_error("%s: empty", name); return MI_ERR_INVALID; }
+    const dim3 grid(grid_for((p->n + 3) / 4, 256), p->B);
+    if (e) hipLaunchKernelGGL(HIP_KERNEL_NAME(posterior_kernel<true, mi_sampler_ext_params>), grid, dim3(256), 0, (hipStream_t)stream, *p, *e);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(posterior_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, *p);
     return mi_check_launch("posterior_kernel");
+}
+extern "C" int mi_posterior_fwd(const mi_posterior_params* p, void* stream) {
+    return posterior_step("mi_posterior_fwd", p, nullptr, stream);
 }
 extern "C" int mi_posterior_ext_fwd(const mi_posterior_params* p, const mi_sampler_ext_params* e, void* stream) {
-    if (!e || !e->x0_prev) return mi_posterior_fwd(p, stream);
-    if (p->B <= 0 || p->n <= 0) { mi_set_error("mi_posterior_ext_fwd: empty"); return MI_ERR_INVALID; }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(posterior_kernel<true, mi_sampler_ext_params>), dim3(grid_for((p->n + 3) / 4, 256), p->B), dim3(256), 0, (hipStream_t)stream, *p, *e);
-    return mi_check_launch("posterior_kernel");
+    return (e && e->x0_prev) ? posterior_step("mi_posterior_ext_fwd", p, e, stream) : posterior_step("mi_posterior_fwd", p, nullptr, stream);
 }
 
+// set: 0 advance by 1 | 1 set to value | 2 advance by value; `mapped`: the entries that take the step -> timestep map from e
+static int step_launch(int* t_state, int64_t* times, int B, int set, int value, bool mapped, const mi_sampler_ext_params* e, void* stream) {
+    if (mapped && (!e || !e->t_map)) { mi_set_error("mapped step kernels: t_map missing"); return MI_ERR_INVALID; }
+    if (mapped) hipLaunchKernelGGL(step_advance_kernel<true>, dim3(1), dim3(64), 0, (hipStream_t)stream, t_state, (long long*)times, B, set, value, e->t_map);
+    else hipLaunchKernelGGL(step_advance_kernel<false>, dim3(1), dim3(64), 0, (hipStream_t)stream, t_state, (long long*)times, B, set, value, (const int*)nullptr);
+    return mi_check_launch(mapped ? "step_advance_mapped_kernel" : "step_advance_kernel");
+}
 extern "C" int mi_step_advance(int* t_state, int64_t* times, int B, void* stream) {
-    hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t_state, (long long*)times, B, 0, 0);
-    return mi_check_launch("step_advance_kernel");
+    return step_launch(t_state, times, B, 0, 0, false, nullptr, stream);
 }
 extern "C" int mi_step_advance_by(int* t_state, int64_t* times, int B, int n, void* stream) {
-    hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t_state, (long long*)times, B, 2, n);
-    return mi_check_launch("step_advance_kernel");
+    return step_launch(t_state, times, B, 2, n, false, nullptr, stream);
 }
 extern "C" int mi_step_set(int* t_state, int64_t* times, int B, int value, void* stream) {
-    hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t_state, (long long*)times, B, 1, value);
-    return mi_check_launch("step_advance_kernel");
-}
-
-static int step_mapped(int* t_state, int64_t* times, int B, int set, int value, const mi_sampler_ext_params* e, void* stream) {
-    if (!e || !e->t_map) { mi_set_error("mapped step kernels: t_map missing"); return MI_ERR_INVALID; }
-    hipLaunchKernelGGL(step_advance_mapped_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t_state, (long long*)times, B, set, value, e->t_map);
-    return mi_check_launch("step_advance_mapped_kernel");
+    return step_launch(t_state, times, B, 1, value, false, nullptr, stream);
 }
 extern "C" int mi_step_advance_mapped(int* t_state, int64_t* times, int B, const mi_sampler_ext_params* e, void* stream) {
-    return step_mapped(t_state, times, B, 0, 0, e, stream);
+    return step_launch(t_state, times, B, 0, 0, true, e, stream);
 }
 extern "C" int mi_step_advance_by_mapped(int* t_state, int64_t* times, int B, int n, const mi_sampler_ext_params* e, void* stream) {
     if (n <= 0) { mi_set_error("mi_step_advance_by_mapped: n = %d", n); return MI_ERR_INVALID; }
-    return step_mapped(t_state, times, B, 2, n, e, stream);
+    return step_launch(t_state, times, B, 2, n, true, e, stream);
 }
 extern "C" int mi_step_set_mapped(int* t_state, int64_t* times, int B, int value, const mi_sampler_ext_params* e, void* stream) {
     if (value < 0) { mi_set_error("mi_step_set_mapped: step %d", value); return MI_ERR_INVALID; }
-    return step_mapped(t_state, times, B, 1, value, e, stream);
+    return step_launch(t_state, times, B, 1, value, true, e, stream);
 }
 
 extern "C" int mi_randn_fill(float* out, int B, int n, uint64_t seed, int sample0, int stream_id, void* stream) {

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from types import SimpleNamespace
 from typing import List, Optional
 
 import torch
@@ -83,23 +84,20 @@ def _lin(m: Optional[nn.Linear]) -> L.MiLinear:
 
 
 class Workspace:
-    pass
+    """Attribute bag of one (shape, precision, lane): buffers, launch plan (``prog*``) and what the sampling loop caches on it."""
+
+    def __init__(self):
+        self.sampler_state = {}      # T | (T, S, sampler, eta) -> sampler.StageState
+        self.step_tables = {}        # prepare_step_tables: (T, t_state pointer[, timesteps]) -> tables of all steps
+        self.prog_stage = None       # the per-step conditioning launches in force (prepare_step_tables)
+        self.prog_stage_off = {}     # stage_prog: (id of a prog_stage list, step offset) -> its copy addressing *t_state - offset
+        self.resize_tabs = {}        # Imagen._lowres_conditioning: source size -> cubic tap tables
 
 
 def _close_workspace(ws):
-    """Destroy the HIP graph execs cached on a workspace's sampler state (Imagen._p_sample_loop): they are raw handles, not tensors."""
-    lib = L.lib()
-    for st in getattr(ws, "sampler_state", {}).values():
-        for entry in getattr(st, "graphs", {}).values():
-            if entry.get("graph") is not None:
-                # sample() never host-syncs its stage streams: replays of this exec (and the workspace buffers it addresses, dropped
-                # together with it) may still be queued -- drain the device first (invalidations are rare: new weights / .to())
-                if L.backend() == "hip-gfx950" and torch.cuda.is_available():
-                    torch.cuda.synchronize(ws.dev)
-                lib.mi_graph_destroy(entry["graph"])
-                entry["graph"] = None
-        if hasattr(st, "graphs"):
-            st.graphs.clear()
+    """Destroy the HIP graph execs cached on a workspace's sampler states: they are raw handles, not tensors."""
+    for st in ws.sampler_state.values():
+        st.close(ws.dev)
 
 
 class UnetEngine:
@@ -216,7 +214,7 @@ class UnetEngine:
         u = self.unet
         dev = next(u.parameters()).device
         lib = L.lib()
-        pk = Workspace()
+        pk = SimpleNamespace()
         pk.keep = []           # keeps packed tensors alive
         pk.freq = P.sinusoid_freq(u.dim, dev)
         pk.conv = {}
@@ -925,9 +923,9 @@ class UnetEngine:
             ws.prog_stage = ws.prog_cond
             return
         key = (T, t_state.data_ptr()) if t_map is None else (T, t_state.data_ptr(), tuple(int(v) for v in t_map))
-        tb = ws.__dict__.setdefault("step_tables", {}).get(key)
+        tb = ws.step_tables.get(key)
         if tb is None:
-            tb = Workspace()
+            tb = SimpleNamespace()
             steps_t = torch.arange(T, dtype=torch.int64, device=dev) if t_map is None else t_map.to(dev, torch.int64).contiguous()
             assert steps_t.numel() == T
             n = T * B2
@@ -986,13 +984,11 @@ class UnetEngine:
     def drop_step_tables(self, ws, t_state: torch.Tensor):
         """Forget the step tables built for ``t_state`` (a sampler stage state that is being evicted), with the offset copies of their
         scatter launches (keyed by the identity of the table's launch list, which a later list could inherit).  The caller has drained the device."""
-        tables = ws.__dict__.get("step_tables", {})
-        for key in [k for k in tables if k[1] == t_state.data_ptr()]:
-            tb = tables.pop(key)
-            cache = ws.__dict__.get("prog_stage_off", {})
-            for k in [k for k in cache if k[0] == id(tb.stage)]:
-                del cache[k]
-            if ws.__dict__.get("prog_stage") is tb.stage:
+        for key in [k for k in ws.step_tables if k[1] == t_state.data_ptr()]:
+            tb = ws.step_tables.pop(key)
+            for k in [k for k in ws.prog_stage_off if k[0] == id(tb.stage)]:
+                del ws.prog_stage_off[k]
+            if ws.prog_stage is tb.stage:
                 ws.prog_stage = ws.prog_cond
 
     def stage_prog(self, ws, t_off: int = 0):
@@ -1002,7 +998,7 @@ class UnetEngine:
         if t_off == 0:
             return ws.prog_stage
         assert ws.prog_stage is not ws.prog_cond, "the step-at-a-time conditioning cannot address a timestep offset"
-        cache = ws.__dict__.setdefault("prog_stage_off", {})
+        cache = ws.prog_stage_off
         key = (id(ws.prog_stage), t_off)
         if key not in cache:
             prog = []

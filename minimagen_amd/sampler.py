@@ -1,0 +1,228 @@
+"""The cascade's reverse-diffusion loop on the device (minimagen/Imagen.py:261-420): what a stage keeps between calls (StageState, on its
+workspace), the launcher of one step's tail kernels, and the captured HIP graphs that replay [U-Net -> tail -> step advance].
+``Imagen._stage_state`` / ``_stage_begin`` / ``_p_sample_loop`` delegate here and pass the knobs of Imagen.py (read there at call time)."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import torch
+
+from . import _lib as L
+from .helpers import quantile_rank
+
+def _drain(dev):
+    if L.backend() == "hip-gfx950" and torch.cuda.is_available():
+        torch.cuda.synchronize(dev)
+
+
+def destroy_graph(entry, dev):
+    """Drain the device, then destroy the captured graph exec of ``entry`` (a dict with a raw handle under "graph"): the one place graph
+    execs go, for every cache in the package.  sample() never host-syncs its stage streams, so replays of the exec (and the buffers it
+    addresses, dropped together with it) may still be queued -- all rare: new weights / .to(), a 9th graph, plan or solver setting."""
+    if entry.get("graph") is not None:
+        _drain(dev)
+        L.lib().mi_graph_destroy(entry["graph"])
+        entry["graph"] = None
+
+
+class StageState:
+    """One stage's loop state, kept on its workspace (so it dies with the buffers it points into) per schedule -- or per (schedule, S,
+    sampler, eta) for a call with ``solver`` = (S, sampler, eta).  Every field is a slot; ``ext`` and ``group_sync`` stay UNSET until they exist
+    (``hasattr`` is how callers ask for a solver extension / a grouped tail); ``t_map`` / ``group_err_host``, None until then, answer the same here."""
+    __slots__ = ("coef", "tau", "t_map", "x0_prev", "ext", "t_state", "x0", "hist", "s_q", "v_q", "seed_dev", "graphs",
+                 "group_sync", "group_err_host", "group_failed", "group_heal")
+
+    def __init__(self, sched, B: int, n: int, dev, solver=None):
+        self.tau = self.t_map = self.x0_prev = None     # the reference's loop has no step -> timestep map and no history
+        if solver is None:
+            self.coef = sched.sampler_coef_table().to(dev).contiguous()
+        else:
+            self.tau, coef = sched.sampler_tables(solver[0], solver[1], solver[2] if solver[1] == 'ddim' else None)
+            self.coef = coef.to(dev).contiguous()
+            self.t_map = self.tau.to(torch.int32).to(dev).contiguous()
+            if solver[1] == 'dpmpp_2m':
+                self.x0_prev = torch.zeros(B, n, dtype=torch.float32, device=dev)
+            self.ext = L.MiSamplerExtParams(L.ptr(self.t_map), L.ptr(self.x0_prev))
+        self.t_state = torch.zeros(1, dtype=torch.int32, device=dev)        # the device-resident step
+        self.x0 = torch.empty(B, n, dtype=torch.float32, device=dev)
+        self.hist = torch.zeros(3 * B * 2 * 2048, dtype=torch.int32, device=dev)
+        self.s_q = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.v_q = torch.zeros(B, 2, dtype=torch.float32, device=dev)
+        self.seed_dev = None            # the Philox seed in device memory (on-device noise): replays of later calls need no re-capture
+        self.graphs = {}                # graph key -> dict(step, graph, keep, per)
+        self.group_err_host = None      # the pinned copy of the grouped tail's error word, allocated with its sync buffer (group_sync)
+        self.group_failed = self.group_heal = False         # a grouped launch gave up: separate kernels from then on / re-zero the buffer
+
+    def close(self, dev):
+        """Drain the device and destroy the captured graph execs (raw handles, not tensors)."""
+        _drain(dev)
+        for entry in self.graphs.values():
+            destroy_graph(entry, dev)
+        self.graphs.clear()
+
+
+def stage_state(ws, sched, B: int, n: int, solver=None, eng=None, max_states: int = 8) -> StageState:
+    """The workspace's state for this schedule / solver setting, keyed by T for the default call and (T, S, sampler, eta) otherwise."""
+    store = ws.sampler_state
+    key = sched.num_timesteps if solver is None else (sched.num_timesteps,) + tuple(solver)
+    st = store.get(key)
+    if st is not None and solver is not None:
+        store[key] = store.pop(key)                      # most recently used last
+    if st is None and solver is not None:
+        # bounded: a caller sweeping S or eta must not grow device memory (a status word still to be polled keeps its state object alive)
+        solver_keys = [k for k in store if isinstance(k, tuple)]
+        while len(solver_keys) >= max_states:
+            old = store.pop(solver_keys.pop(0))
+            old.close(ws.dev)
+            if eng is not None:
+                eng.drop_step_tables(ws, old.t_state)
+    if st is None:
+        st = store[key] = StageState(sched, B, n, ws.dev, solver)
+    return st
+
+
+def stage_begin(unet, shape, *, noise_scheduler, ws, noise_fn=None, seed: int = 0, sample0: int = 0, stage: int = 0, solver=None, max_states: int = 8):
+    """Everything of a stage's loop that does not depend on the PREVIOUS stage's image: x_T (Imagen.py:400), the device-resident timestep, the
+    per-step conditioning tables of all T steps.  sample() issues it for every stage before the first stage's loop, so that a later stage's
+    stream has it done while it waits for its low-resolution input (on-device noise only: injected noise is drawn in the reference's order)."""
+    lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
+    B, n = shape[0], shape[1] * shape[2] * shape[3]
+    T = noise_scheduler.num_timesteps if solver is None else solver[0]        # steps of the loop (one draw each, for every solver)
+    st = stage_state(ws, noise_scheduler, B, n, solver, eng, max_states)
+    noise_dev = None
+    if noise_fn is not None:
+        ws.x.copy_(noise_fn(shape))                                          # Imagen.py:400
+        noise_dev = torch.stack([noise_fn(shape) for _ in range(T)]).to(ws.dev).contiguous()   # Imagen.py:361, in step order
+    else:
+        L.check(lib.mi_randn_fill(L.ptr(ws.x), B, n, seed, sample0, (stage << 20) | (1 << 19) | 1, stream), "mi_randn_fill")
+    if st.t_map is None:
+        L.check(lib.mi_step_set(L.ptr(st.t_state), L.ptr(ws.times), B, T - 1, stream), "mi_step_set")
+    else:
+        # the device-resident state is the STEP index; the U-Net's conditioning sees the trained timestep t_map[step]
+        L.check(lib.mi_step_set_mapped(L.ptr(st.t_state), L.ptr(ws.times), B, T - 1, C.byref(st.ext), stream), "mi_step_set_mapped")
+    if st.x0_prev is not None:
+        st.x0_prev.zero_()                                       # the first step's history coefficient is 0: 0 * stale must not be NaN
+    eng.prepare_step_tables(ws, T, st.t_state, stream, t_map=st.tau)         # (timestep, text)-only conditioning of all T steps, once
+    return st, noise_dev
+
+
+def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream):
+    """What follows the U-Net evaluation in a step, fixed once per graph entry -> (launch, advance): ``launch(k)`` enqueues the tail kernels of
+    step *t_state - k (``kind``: "small" one workgroup per image | "group" cooperating workgroups | "separate" kernels), ``advance(n)`` moves the
+    device-resident step by n (mapped entries when the state has a step -> timestep map).  Always the *_ext_fwd tails: without st.ext / a history buffer they ARE the plain ones."""
+    lib, tails = L.lib(), {}
+    ext, q_ = (C.byref(st.ext) if st.t_map is not None else None), C.byref(qp)
+    state = (L.ptr(st.t_state), L.ptr(ws.times), cp.B)
+
+    def params(k):
+        if k not in tails:
+            c_, p_ = L.MiCfgX0Params.from_buffer_copy(cp), L.MiPosteriorParams.from_buffer_copy(pp)
+            c_.t_off = p_.t_off = k
+            if kind != "separate":
+                c_.x0 = c_.hist0 = 0                      # x0 stays in registers, the histograms in LDS (and per-image counters)
+            tails[k] = (C.byref(c_), q_, C.byref(p_))                # (the references keep the blocks alive)
+        return tails[k]
+
+    def small(k=0):
+        L.check(lib.mi_sampler_step_small_ext_fwd(*params(k), ext, stream), "mi_sampler_step_small_ext_fwd")
+
+    def group(k=0):
+        L.check(lib.mi_sampler_step_group_ext_fwd(*params(k), ext, L.ptr(st.group_sync), stream), "mi_sampler_step_group_ext_fwd")
+
+    def separate(k=0):
+        c_, _, p_ = params(k)
+        L.check(lib.mi_cfg_x0_fwd(c_, stream), "mi_cfg_x0_fwd")
+        L.check(lib.mi_quantile_fwd(q_, stream), "mi_quantile_fwd")
+        L.check(lib.mi_posterior_ext_fwd(p_, ext, stream), "mi_posterior_ext_fwd")
+
+    if st.t_map is None:
+        advance = lambda n=1: L.check(lib.mi_step_advance_by(*state, n, stream), "mi_step_advance_by")
+    else:
+        advance = lambda n=1: L.check(lib.mi_step_advance_by_mapped(*state, n, ext, stream), "mi_step_advance_by_mapped")
+    return dict(small=small, group=group, separate=separate)[kind], advance
+
+
+def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, noise_fn=None, seed: int = 0, sample0: int = 0,
+                  stage: int = 0, use_graph: bool = True, begun=None, solver=None, group_max: int = 8, max_states: int = 8):
+    """Imagen.py:373-420 + :329-370 + :261-326: T replays of [U-Net (both guidance halves) -> CFG combine + x0 -> dynamic-threshold quantile ->
+    posterior draw -> t -= 1].  ``solver`` = (S, sampler, eta): S steps over a subsequence of the trained timesteps; the loop, the noise index and the
+    Philox stream count STEPS: the reference's loop with T = S but for the state's step -> timestep map and history buffer (``st.ext``)."""
+    lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
+    B, Cc, H, W = shape
+    n = Cc * H * W
+    T = noise_scheduler.num_timesteps if solver is None else solver[0]
+    two = ws.B2 != ws.B
+    if begun is None:
+        begun = stage_begin(unet, shape, noise_scheduler=noise_scheduler, ws=ws, noise_fn=noise_fn, seed=seed, sample0=sample0, stage=stage, solver=solver, max_states=max_states)
+    st, noise_dev = begun
+    k_lo, k_hi, w = quantile_rank(n, im.dynamic_thresholding_percentile)
+    # the whole tail in one launch: of one workgroup per image (n <= MI_SAMPLER_SMALL_N), or of <= group_max (0: never) cooperating workgroups -- but
+    # for a stage state whose grouped launch ever failed (fail-stop: NaN images + the sticky error word, see Imagen._poll_status)
+    fused = os.environ.get("MINIMAGEN_SAMPLER_FUSED", "1") != "0"
+    grouped = fused and 0 < lib.mi_sampler_group_size(n) <= group_max and not st.group_failed
+    kind = "small" if (fused and n <= 16384) else "group" if grouped else "separate"
+    group = kind == "group"
+    if st.group_heal:
+        st.group_sync.zero_()               # stream-ordered behind every launch queued on this lane: ticket, counters, histograms, error word
+        st.group_heal = False
+    # the captured graph of `per` steps is cached per (workspace, guidance, threshold, noise mode, shard offset, tail kind); the seed is in device memory
+    gkey = (float(cond_scale), two, k_lo, k_hi, w, sample0, stage, T, noise_dev is None, group) + (() if solver is None else (tuple(solver),))
+    entry = st.graphs.get(gkey) if (use_graph and noise_dev is None) else None
+    seed = int(seed) & 0x7FFFFFFFFFFFFFFF
+    if noise_dev is None:
+        if st.seed_dev is None:
+            st.seed_dev = torch.zeros(1, dtype=torch.int64, device=ws.dev)
+        st.seed_dev.fill_(seed)
+    if entry is None:
+        # the radix select's first pass rides on the producer of x0; st.hist is zero on allocation and every mi_quantile_fwd leaves it zeroed again
+        cp = L.MiCfgX0Params(B, n, L.ptr(ws.pred), 1 if two else 0, float(cond_scale), L.ptr(ws.x), L.ptr(st.coef), L.ptr(st.t_state), 0, L.ptr(st.x0), L.ptr(st.hist))
+        qp = L.MiQuantileParams(B, n, L.ptr(st.x0), k_lo, k_hi, w, L.ptr(st.hist), L.ptr(st.s_q), L.ptr(st.v_q), 1, 1)
+        pp = L.MiPosteriorParams(B, n, T, L.ptr(st.x0), L.ptr(st.s_q), L.ptr(ws.x), L.ptr(st.coef), L.ptr(st.t_state),
+                                 L.ptr(noise_dev), seed, sample0, stage << 20, L.ptr(st.seed_dev) if noise_dev is None else 0)
+        if group and st.group_err_host is None:
+            st.group_sync = torch.zeros(lib.mi_sampler_group_sync_bytes(B, n), dtype=torch.uint8, device=ws.dev)   # this workspace's launches only
+            st.group_err_host = torch.zeros(1, dtype=torch.int32).pin_memory() if L.backend() == "hip-gfx950" else torch.zeros(1, dtype=torch.int32)
+        launch, advance = tail_launcher(st, ws, kind, cp, qp, pp, stream)
+
+        def one_step(k=0, by=1):                 # step *t_state - k, then the device-resident step moves by `by`
+            eng.run_step(ws, stream, t_off=k)
+            launch(k)
+            if by:
+                advance(by)
+        # `per` steps per captured graph (one replay boundary, ~9 us of idle GPU, per graph): step k addresses *t_state - k, one advance per graph
+        cap = int(os.environ.get("MINIMAGEN_STEPS_PER_GRAPH", "5"))
+        per = next(k for k in (5, 4, 3, 2, 1) if k <= cap and T % k == 0)
+        entry = dict(step=one_step, graph=None, per=per)
+        if use_graph:
+            offsets = eng.step_offsets_supported(ws)
+            L.check(lib.mi_graph_begin(stream), "mi_graph_begin")
+            try:
+                for k in range(per):
+                    one_step(k, per if k == per - 1 else 0) if offsets else one_step()
+            finally:
+                g = C.c_void_p()
+                rc = lib.mi_graph_end(stream, C.byref(g))
+            L.check(rc, "mi_graph_end")
+            entry["graph"] = g
+            if noise_dev is None:
+                while len(st.graphs) >= 8:                   # bounded: one exec per (guidance, threshold, shard offset) combination
+                    destroy_graph(st.graphs.pop(next(iter(st.graphs))), ws.dev)
+                st.graphs[gkey] = entry
+    if use_graph:
+        try:
+            for _ in range(T // entry["per"]):
+                L.check(lib.mi_graph_launch(entry["graph"], stream), "mi_graph_launch")
+        finally:
+            if noise_dev is not None:          # one-off graph (injected noise buffer): the exec must outlive its replays
+                destroy_graph(entry, ws.dev)
+    else:
+        for _ in range(T):
+            entry["step"]()
+    img = torch.empty(shape, dtype=torch.float32, device=ws.dev)
+    L.check(lib.mi_finalize_images(L.ptr(ws.x), L.ptr(img), B * n, 1 if im.auto_normalize_img else 0, stream), "mi_finalize_images")
+    if group:
+        # the sticky error word goes to pinned host memory behind the stage's last launch; Imagen._poll_status reads it once this call's event has fired
+        st.group_err_host.copy_(st.group_sync[8:12].view(torch.int32), non_blocking=True)
+        im._status_stages.append((st, stage, (B, H, W)))
+    return img

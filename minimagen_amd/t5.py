@@ -8,6 +8,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib as L
+from .sampler import destroy_graph
 
 MAX_LENGTH = 256
 DEFAULT_T5_NAME = 't5_small'
@@ -106,11 +107,7 @@ class T5EncoderHIP:
                       h=e(M, d), sq=e(M, -(-d // 64)), sq2=e(M, -(-d // 64)), qkv=e(M, 3 * inner), ctx=e(M, inner), ff=e(M, c["d_ff"]), h2=e(M, d), out=e(M, d),
                       bias=self.bias_table(Lq), graph=None)
             while len(plans) >= 8:                         # bounded: one plan per shape
-                old = plans.pop(next(iter(plans)))
-                if old["graph"] is not None:
-                    if L.backend() == "hip-gfx950":
-                        torch.cuda.synchronize(self.dev)
-                    L.lib().mi_graph_destroy(old["graph"])
+                destroy_graph(plans.pop(next(iter(plans))), self.dev)
             plans[(B, Lq)] = pl
         return pl
 
