@@ -379,6 +379,40 @@ int mi_step_set_mapped(int* t_state, int64_t* times, int B, int value, const mi_
 int mi_step_advance_mapped(int* t_state, int64_t* times, int B, const mi_sampler_ext_params* e, void* stream);
 int mi_step_advance_by_mapped(int* t_state, int64_t* times, int B, int n, const mi_sampler_ext_params* e, void* stream);
 
+/* ---- inpainting: pixels the caller already has are re-imposed at the noise level of every denoising step.  The coefficient table's
+ * columns 6 and 7 hold, for the step at row k, sqrt(abar_{k-1}) and sqrt(1 - abar_{k-1}) (row 0: exactly 1 and 0).  Behind the step's
+ * x_{k-1} -- computed exactly as without this block: the threshold quantile is taken over the whole image, x0_prev gets the thresholded x0 of
+ * every element -- the tails replace the known pixels, per element, every operation rounded on its own, in this order (identical in the
+ * three forms):
+ *   x = mask ? row[6]*y + row[7]*z' : x        i.e. fadd(fmul(row[6], y), fmul(row[7], z'))
+ * with y = known[b][i], mask = mask[b][i % hw] and z' the draw of blend j = (T-1-k) + 1 (T: mi_posterior_params.T, the number of steps):
+ * known_noise[j][b][i] or, when known_noise == NULL, Philox stream known_stream + j with the (seed, sample0 + b, quad) keying of the step
+ * noise.  At row 0 (the last blend) no draw is read or generated and the known pixels become y bit for bit.  Blend 0 (behind x_T, with
+ * a = sqrt(abar_{T-1}), b = sqrt(1 - abar_{T-1}) from the caller) is mi_inpaint_blend0_fwd.  In the grouped tail a workgroup that fails
+ * (fail-stop, above) leaves before the blend: its part of the image is NaN, known pixels included.
+ * Struct index 25 of mi_struct_size; added within ABI 12 (no existing struct or entry changed). */
+typedef struct mi_inpaint_params {
+    const float* known;           /* [B][n] the known image in the sampler's range */
+    const unsigned char* mask;    /* [B][hw] nonzero: the pixel is known; element i of an image uses pixel i % hw.  4-byte aligned when hw % 4 == 0 */
+    int hw;                       /* pixels per channel plane: > 0 and a divisor of n */
+    int known_stream;             /* Philox stream of blend 0; blend j draws from known_stream + j */
+    const float* known_noise;     /* [T][B][n] injected draws of blends 0 .. T-1, or NULL (Philox) */
+    long long reserved[2];        /* zero */
+} mi_inpaint_params;
+/* the *_ext_fwd tails plus the masked replace.  e may be NULL or carry no x0_prev (no history term); ip == NULL: exactly the *_ext_fwd entry.
+ * MI_ERR_INVALID for a block without known / mask, with hw <= 0 or with n % hw != 0. */
+int mi_posterior_inpaint_fwd(const mi_posterior_params* p, const mi_sampler_ext_params* e, const mi_inpaint_params* ip, void* stream);
+int mi_sampler_step_small_inpaint_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e,
+                                      const mi_inpaint_params* ip, void* stream);
+int mi_sampler_step_group_inpaint_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e,
+                                      const mi_inpaint_params* ip, void* sync, void* stream);
+/* blend 0: x[b][i] = mask ? a*y + b*z'_0 : x[b][i], same operation order, z'_0 = ip->known_noise[0][b][i] or Philox stream ip->known_stream */
+int mi_inpaint_blend0_fwd(float* x, int B, int n, const mi_inpaint_params* ip, float a, float b, uint64_t seed, int sample0, void* stream);
+/* a stage's known image and mask from the caller's, already at the stage's size (img [B][n]): known = clamp(img, 0, 1), then *2-1 when
+ * normalize != 0; mask_out [B][size*size] = mask_in [B][Hin][Win] != 0 at the nearest-neighbour source index floor(i * Hin / size) */
+int mi_inpaint_prepare_fwd(const float* img, float* known, int B, int n, int normalize, const unsigned char* mask_in, int Hin, int Win, unsigned char* mask_out,
+                           int size, void* stream);
+
 /* N(0,1) fill with the same generator as mi_posterior_fwd (x_T, low-res augmentation noise) */
 int mi_randn_fill(float* out, int B, int n, uint64_t seed, int sample0, int stream_id, void* stream);
 

@@ -2,7 +2,6 @@
 reverse-diffusion loop runs as HIP kernels replayed from a HIP graph on MI355X."""
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Callable, List, Literal, Tuple, Union
 
@@ -14,7 +13,7 @@ from . import _lib as L
 from . import sampler as S
 from .Unet import Unet
 from .diffusion_model import GaussianDiffusion
-from .helpers import (cast_tuple, cubic_taps, default, eval_decorator, exists, module_device, normalize_neg_one_to_one, resize_image_to)
+from .helpers import (cast_tuple, default, eval_decorator, exists, module_device, normalize_neg_one_to_one, resize_image_to)
 from .t5 import get_encoded_dim, t5_encode_text
 
 # the sampler tail of images too large for one workgroup (the super-resolution stages) as ONE launch of cooperating workgroups
@@ -200,6 +199,56 @@ class Imagen(nn.Module):
             out.append(None if (S == T and name == 'ddpm') else (S, name, eta))
         return out
 
+    def _parse_inpaint(self, batch_size: int, inpaint_images, inpaint_masks, start_image, start_at_stage, stop_at_stage):
+        """-> (first stage, one past the last stage, (images float32 [B, C, H, W], masks uint8 [B, Hm, Wm]) or None, start image float32 or None),
+        the tensors still where the caller has them.  Host only; raises ValueError on bad or inconsistent values."""
+        n_stages = len(self.unets)
+
+        def stage_index(v, name, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f"{name} must be an int in [{lo}, {hi}] for a cascade of {n_stages} stages, got {v!r}")
+            return v
+
+        def images(t, name):
+            if not torch.is_tensor(t) or t.dim() != 4 or not t.is_floating_point():
+                raise ValueError(f"{name} must be a float tensor [B, {self.channels}, H, W]")
+            if t.shape[0] != batch_size:
+                raise ValueError(f"{name}: batch {t.shape[0]} does not match the text batch {batch_size}")
+            if t.shape[1] != self.channels:
+                raise ValueError(f"{name}: {t.shape[1]} channels, the model has {self.channels}")
+            if t.shape[2] != t.shape[3] or t.shape[2] < 1:
+                raise ValueError(f"{name} must be square, got {tuple(t.shape[2:])}")
+            return t.detach().to(torch.float32)
+
+        stop = n_stages if stop_at_stage is None else stage_index(stop_at_stage, "stop_at_stage", 1, n_stages)
+        start = 0
+        if (start_image is None) != (start_at_stage is None):
+            raise ValueError("start_image and start_at_stage go together")
+        if start_at_stage is not None:
+            start = stage_index(start_at_stage, "start_at_stage", 1, n_stages - 1)
+            if start >= stop:
+                raise ValueError(f"start_at_stage = {start} must be below stop_at_stage = {stop}")
+            if not self.unets[start].lowres_cond:
+                raise ValueError(f"stage {start} takes no low-resolution conditioning image: it cannot start from one")
+            start_image = images(start_image, "start_image")
+        inpaint = None
+        if (inpaint_images is None) != (inpaint_masks is None):
+            raise ValueError("inpaint_images and inpaint_masks go together")
+        if inpaint_images is not None:
+            inpaint_images = images(inpaint_images, "inpaint_images")
+            m = inpaint_masks
+            if not torch.is_tensor(m) or m.dim() not in (3, 4) or (m.dim() == 4 and m.shape[1] != 1):
+                raise ValueError("inpaint_masks must be a tensor [B, H, W] or [B, 1, H, W]")
+            if m.shape[0] != batch_size:
+                raise ValueError(f"inpaint_masks: batch {m.shape[0]} does not match the text batch {batch_size}")
+            m = m.detach().reshape(m.shape[0], m.shape[-2], m.shape[-1])
+            if m.shape[1] < 1 or m.shape[2] < 1:
+                raise ValueError("inpaint_masks: empty")
+            if m.dtype != torch.bool and not bool(((m == 0) | (m == 1)).all()):
+                raise ValueError("inpaint_masks must hold 0 / 1 (or be bool)")
+            inpaint = (inpaint_images, m.to(torch.uint8))
+        return start, stop, inpaint, start_image
+
     def _lowres_conditioning(self, unet: Unet, img, image_size: int, ws, lowres_noise_level: float, noise_fn, seed, sample0, stage):
         """Imagen.py:479-485 + :393: cubic resize (reflect pad) -> q_sample at int(T*level) -> *2-1."""
         lib = L.lib()
@@ -207,22 +256,7 @@ class Imagen(nn.Module):
         B, Cc, Hin, Win = img.shape
         t_low = int(self.lowres_noise_schedule.num_timesteps * lowres_noise_level)          # diffusion_model.py:68-69
         ws.lowres_times.fill_(t_low)
-        if Hin != image_size:
-            # tap tables: built and uploaded once per (workspace, source size) -- an upload from pageable host memory per call would
-            # block the host behind the previous call still running on this stage's stream
-            cache = ws.resize_tabs
-            if (Hin, Win) not in cache:
-                _, idx_h, w_h = cubic_taps(Hin, image_size)
-                _, idx_w, w_w = cubic_taps(Win, image_size)
-                cache[(Hin, Win)] = ([t.to(ws.dev) for t in (idx_h, w_h, idx_w, w_w)], idx_h.shape[1], idx_w.shape[1])
-            tabs, kh, kw = cache[(Hin, Win)]
-            up = torch.empty(B, Cc, image_size, image_size, dtype=torch.float32, device=ws.dev)
-            rp = L.MiResizeParams(B * Cc, Hin, Win, image_size, image_size, kh, kw, L.ptr(img), L.ptr(up),
-                                  L.ptr(tabs[0]), L.ptr(tabs[1]), L.ptr(tabs[2]), L.ptr(tabs[3]))
-            L.check(lib.mi_resize_fwd(C.byref(rp), stream), "mi_resize_fwd")
-            ws.resize_keepalive = tabs
-        else:
-            up = img
+        up = S.cubic_resize(ws, img, image_size, stream)
         n = Cc * image_size * image_size
         if noise_fn is not None:
             noise = noise_fn(up.shape).to(ws.dev).contiguous()                  # Imagen.py:485 randn_like
@@ -241,7 +275,9 @@ class Imagen(nn.Module):
                cond_scale: float = 1., lowres_sample_noise_level: float = None, return_pil_images: bool = False,
                device: torch.device = None, *, _noise: Callable = None, _seed: int = 1234, _sample_offset: int = 0,
                _use_graph: bool = True, _precision: str = None, _async: bool = False, _revalidated: bool = False,
-               sample_steps: Union[int, List[int], Tuple[int, ...]] = None, sampler: str = None, sampler_eta: float = None):
+               sample_steps: Union[int, List[int], Tuple[int, ...]] = None, sampler: str = None, sampler_eta: float = None,
+               inpaint_images: torch.Tensor = None, inpaint_masks: torch.Tensor = None, start_image: torch.Tensor = None,
+               start_at_stage: int = None, stop_at_stage: int = None):
         """minimagen/Imagen.py:424-510.  Private keyword-only extras (not in the reference): ``_noise(shape)`` injects a
         host noise stream in the reference's draw order (parity runs); otherwise noise is Philox keyed by
         (``_seed``, ``_sample_offset`` + row, stage, step, element) so a sharded batch reproduces the unsharded one;
@@ -254,9 +290,23 @@ class Imagen(nn.Module):
         ``sampler`` = 'ddpm' (default: the reference's ancestral step on the subsequence), 'ddim' (eta = ``sampler_eta``, default 0) or
         'dpmpp_2m' (DPM-Solver++ 2M on the thresholded x0, deterministic); ``sampler_eta`` in [0, 1] goes with 'ddim' only.  A call with
         none of them, or with S = T and 'ddpm', IS the reference's loop (same tables, graphs and kernels as before these arguments
-        existed).  Tables: GaussianDiffusion.sampler_tables.  Bad values raise ValueError before anything is launched."""
+        existed).  Tables: GaussianDiffusion.sampler_tables.  Bad values raise ValueError before anything is launched.
+
+        Conditioning on pixels the caller has (keyword-only, not in the reference).  ``inpaint_images`` ([B, C, H, W]
+        float in [0, 1], square, any size) with ``inpaint_masks`` ([B, H, W] or [B, 1, H, W], bool or 0/1, nonzero = "known, keep"): every
+        stage re-imposes the known pixels -- the images resized to its size (cubic, antialiased when shrinking), the masks by nearest
+        neighbour -- at the noise level of EVERY step, inside the sampler tails, for every ``sampler`` / ``sample_steps``; the returned
+        images carry them.  One pass per step: no RePaint resampling.  ``start_image`` ([B, C, H, W] in [0, 1], square, any size) with
+        ``start_at_stage`` = s >= 1 skips the stages below s and stands in for the output of stage s - 1 (run only the super-resolution
+        stage on an image of the caller's); ``stop_at_stage`` = s runs the stages below s and returns that stage's image.  The noise is
+        keyed by the stage INDEX, so a cascade cut in two this way gives the bits of the whole.  A call with none of these goes through
+        exactly the states, tables, graphs and kernels it went through before they existed."""
         solvers = self._parse_solver(sample_steps, sampler, sampler_eta)
-        call_args = dict(sample_steps=sample_steps, sampler=sampler, sampler_eta=sampler_eta, texts=texts, text_masks=text_masks, text_embeds=text_embeds, cond_scale=cond_scale, lowres_sample_noise_level=lowres_sample_noise_level,
+        if exists(text_embeds) or exists(texts):
+            first_stage, end_stage, inpaint, start_image = self._parse_inpaint(text_embeds.shape[0] if exists(text_embeds) else len(texts), inpaint_images,
+                                                                               inpaint_masks, start_image, start_at_stage, stop_at_stage)
+        call_args = dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, start_image=start_image, start_at_stage=start_at_stage,
+                         stop_at_stage=stop_at_stage, sample_steps=sample_steps, sampler=sampler, sampler_eta=sampler_eta, texts=texts, text_masks=text_masks, text_embeds=text_embeds, cond_scale=cond_scale, lowres_sample_noise_level=lowres_sample_noise_level,
                          return_pil_images=return_pil_images, device=device, _noise=_noise, _seed=_seed, _sample_offset=_sample_offset,
                          _use_graph=_use_graph, _precision=_precision, _async=_async)
         device = default(device, self.device)
@@ -279,6 +329,11 @@ class Imagen(nn.Module):
         keep = torch.cat((torch.ones(batch_size, dtype=torch.bool), torch.zeros(B2 - batch_size, dtype=torch.bool)))
         text_embeds = text_embeds.to(device)
         text_masks = text_masks.to(device) if exists(text_masks) else None
+        if inpaint is not None:
+            inpaint = tuple(t.to(device).contiguous() for t in inpaint) + (self.auto_normalize_img,)
+        if start_image is not None:
+            start_image = start_image.to(device).contiguous()
+        pixel_inputs = [t for t in (inpaint or ())[:2] + (start_image,) if t is not None]
 
         # One HIP stream PER STAGE (graphs cannot be captured on the legacy default stream anyway).  Within a call stage s + 1 waits for
         # stage s through an event; ACROSS calls the stages form a pipeline: with ``_async=True`` the caller's stream is never made to
@@ -327,7 +382,8 @@ class Imagen(nn.Module):
             inputs_ready = caller_stream.record_event()
         from .helpers import null_context
         precision = _precision if _precision is not None else os.environ.get("MINIMAGEN_PRECISION", "fp32")
-        stages = list(enumerate(zip(self.unets, self.sample_channels, self.image_sizes, self.noise_schedulers)))
+        stages = list(enumerate(zip(self.unets, self.sample_channels, self.image_sizes, self.noise_schedulers)))[first_stage:end_stage]
+        known = {} if inpaint is None else dict(inpaint=inpaint)        # (a call without known pixels passes nothing new down)
         # ---- pass 1, every stage on its own stream: what depends on the CAPTIONS only (text conditioning, the folded context rows, x_T, the
         # step tables) -- issued for all stages up front, so a later stage has it behind it when its low-resolution input arrives
         wss, begun = {}, {}
@@ -337,7 +393,7 @@ class Imagen(nn.Module):
                 # the stage streams read the caller's tensors after sample() has returned (_async) / after the caller may have dropped
                 # them: tell the caching allocator, or a block freed on the caller's stream could be handed out again while a stage's
                 # text_cond launch is still queued
-                for t_in in (text_embeds, text_masks):
+                for t_in in (text_embeds, text_masks, *pixel_inputs):
                     if t_in is not None and t_in.is_cuda:
                         t_in.record_stream(streams[stage])
             with (torch.cuda.stream(streams[stage]) if on_gpu else null_context()):
@@ -350,9 +406,9 @@ class Imagen(nn.Module):
                     ws.lowres_times.fill_(int(self.lowres_noise_schedule.num_timesteps * lowres_sample_noise_level))
                 if _noise is None:
                     begun[stage] = self._stage_begin(unet, (batch_size, self.channels, image_size, image_size), noise_scheduler=noise_scheduler,
-                                                     ws=ws, seed=_seed, sample0=_sample_offset, stage=stage, solver=solvers[stage])
+                                                     ws=ws, seed=_seed, sample0=_sample_offset, stage=stage, solver=solvers[stage], **known)
         # ---- pass 2: the cascade
-        img, prev_done = None, None
+        img, prev_done = start_image, None
         for stage, (unet, channel, image_size, noise_scheduler) in stages:
             if on_gpu and prev_done is not None:
                 streams[stage].wait_event(prev_done)
@@ -364,7 +420,7 @@ class Imagen(nn.Module):
                     self._lowres_conditioning(unet, img, image_size, ws, lowres_sample_noise_level, _noise, _seed, _sample_offset, stage)
                 img = self._p_sample_loop(unet, (batch_size, self.channels, image_size, image_size), noise_scheduler=noise_scheduler,
                                           ws=ws, cond_scale=cond_scale, noise_fn=_noise, seed=_seed, sample0=_sample_offset,
-                                          stage=stage, use_graph=_use_graph, begun=begun.get(stage), solver=solvers[stage])
+                                          stage=stage, use_graph=_use_graph, begun=begun.get(stage), solver=solvers[stage], **known)
                 if on_gpu:
                     prev_done = streams[stage].record_event()
         pack_tokens = [] if (_noise is not None or _revalidated) else [(unet.engine(), unet.engine().pack_begin()) for unet in self.unets]

@@ -140,6 +140,11 @@ class MiSamplerExtParams(C.Structure):
     _fields_ = [("t_map", C.c_void_p), ("x0_prev", C.c_void_p), ("reserved", C.c_longlong * 2)]
 
 
+class MiInpaintParams(C.Structure):
+    _fields_ = [("known", C.c_void_p), ("mask", C.c_void_p), ("hw", C.c_int), ("known_stream", C.c_int), ("known_noise", C.c_void_p),
+                ("reserved", C.c_longlong * 2)]
+
+
 class MiResizeParams(C.Structure):
     _fields_ = [("planes", C.c_int), ("Hin", C.c_int), ("Win", C.c_int), ("Hout", C.c_int), ("Wout", C.c_int), ("KH", C.c_int), ("KW", C.c_int),
                 ("in_", C.c_void_p), ("out", C.c_void_p), ("idx_h", C.c_void_p), ("w_h", C.c_void_p), ("idx_w", C.c_void_p), ("w_w", C.c_void_p)]
@@ -196,7 +201,7 @@ class MiPackConv3Desc(C.Structure):
 _STRUCTS = {0: MiAct, 1: MiConvParams, 2: MiCrossEmbedParams, 3: MiLinear, 4: MiTextCondParams, 5: MiCondStepParams,
             6: MiAttnFoldParams, 7: MiCrossAttnParams, 8: MiCfgX0Params, 9: MiQuantileParams, 10: MiPosteriorParams,
             11: MiResizeParams, 12: MiSelfAttnParams, 13: MiChanFFParams, 14: MiFlashAttnParams, 15: MiTokensToNchwParams, 16: MiConvWgradParams, 17: MiBlockBwdParams, 18: MiCrossEmbedWgradParams, 19: MiFoldedAttnParams, 20: MiAdamTensor, 21: MiAdamParams, 22: MiPackConv3Desc,
-            23: MiFlashAttnTrainParams, 24: MiSamplerExtParams}
+            23: MiFlashAttnTrainParams, 24: MiSamplerExtParams, 25: MiInpaintParams}
 
 _lib = None
 _backend = None
@@ -240,6 +245,11 @@ def _bind(lib):
     lib.mi_step_set_mapped.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.mi_step_advance_mapped.argtypes = [vp, vp, i32, vp, vp]
     lib.mi_step_advance_by_mapped.argtypes = [vp, vp, i32, i32, vp, vp]
+    lib.mi_posterior_inpaint_fwd.argtypes = [vp, vp, vp, vp]
+    lib.mi_sampler_step_small_inpaint_fwd.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.mi_sampler_step_group_inpaint_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.mi_inpaint_blend0_fwd.argtypes = [vp, i32, i32, vp, f32, f32, u64, i32, vp]
+    lib.mi_inpaint_prepare_fwd.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, vp, i32, vp]
     lib.mi_randn_fill.argtypes = [vp, i32, i32, u64, i32, i32, vp]
     lib.mi_finalize_images.argtypes = [vp, vp, i64, i32, vp]
     lib.mi_lowres_augment.argtypes = [vp, vp, vp, i64, f32, f32, i32, vp]

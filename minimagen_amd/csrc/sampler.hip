@@ -117,6 +117,52 @@ __device__ __forceinline__ void step_noise4(const mi_posterior_params& pp, int b
     else randn4(pp.seed_dev ? *pp.seed_dev : pp.seed, (unsigned)(pp.sample0 + b), (unsigned)(pp.stream_base + k), (unsigned)qd, z);
 }
 
+// ------------------------------------------------------------------ the known region of an inpainting call (mi_inpaint_params)
+// coefficient columns 6 and 7 of the step's row: sqrt(abar_{k-1}), sqrt(1 - abar_{k-1})
+struct known_coef { float c6, c7; };
+__device__ __forceinline__ known_coef load_known_coef(const float* coef, int t) { return {coef[t * 8 + 6], coef[t * 8 + 7]}; }
+
+// the mask bytes of the four elements from i (a multiple of 4) of image b: element i uses pixel i % hw.  One 4-byte load when hw % 4 == 0 (a
+// quad then lies inside one channel), else byte by byte -- a quad may straddle two channels; past the row's end: 0
+__device__ __forceinline__ void ld_mask4(const mi_inpaint_params& ip, int b, int i, int n, unsigned char (&m)[4]) {
+    const unsigned char* row = ip.mask + (size_t)b * ip.hw;
+    if ((ip.hw & 3) == 0) {
+        const unsigned w = *reinterpret_cast<const unsigned*>(row + i % ip.hw);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m[e] = (unsigned char)(w >> (8 * e));
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m[e] = (i + e < n) ? row[(i + e) % ip.hw] : (unsigned char)0;
+    }
+}
+
+// the masked replace of one quad: v = m ? a*y + b*z' : v, fadd(fmul(a, y), fmul(b, z')), every operation rounded on its own.  `j`: the blend's
+// index (0 behind x_T, s + 1 in the tail of the step counted s from the first) = the index of its draw, from the injected buffer [S][B][n] or
+// Philox stream known_stream + j with the step noise's (seed, row, quad) keying; j < 0: no draw, neither read nor generated -- the known
+// pixels become y itself (the last blend, whose row holds (1, 0)).  The known image and the mask are read once; a quad without a known pixel draws nothing.
+__device__ __forceinline__ void known_blend4(const mi_inpaint_params& ip, unsigned long long seed, int sample0, int B, int b, int j, int qd, int n, bool vec,
+                                             float a, float bcoef, float (&v)[4]) {
+    unsigned char m[4];
+    ld_mask4(ip, b, 4 * qd, n, m);
+    if (!(m[0] | m[1] | m[2] | m[3])) return;
+    float y[4], z[4];
+    ld_quad(ip.known + (size_t)b * n, 4 * qd, n, vec, y);
+    if (j < 0) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (m[e]) v[e] = y[e];
+        return;
+    }
+    if (ip.known_noise) ld_quad(ip.known_noise + ((size_t)j * B + b) * n, 4 * qd, n, vec, z);
+    else randn4(seed, (unsigned)(sample0 + b), (unsigned)(ip.known_stream + j), (unsigned)qd, z);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) if (m[e]) v[e] = __fadd_rn(__fmul_rn(a, y[e]), __fmul_rn(bcoef, z[e]));
+}
+// ... in the tail of the step at coefficient row t (k = T - 1 - t steps behind the first): blend k + 1 with columns 6 and 7, no draw at row 0
+__device__ __forceinline__ void known_step4(const mi_inpaint_params& ip, const mi_posterior_params& pp, int b, int t, int k, int qd, int n, bool vec, float (&v)[4]) {
+    const known_coef kc = load_known_coef(pp.coef, t);
+    known_blend4(ip, pp.seed_dev ? *pp.seed_dev : pp.seed, pp.sample0, pp.B, b, t > 0 ? k + 1 : -1, qd, n, vec, kc.c6, kc.c7, v);
+}
+
 // ------------------------------------------------------------------ K11 epilogue
 template <bool HIST>
 __global__ __launch_bounds__(256) void cfg_x0_kernel(const mi_cfg_x0_params p) {
@@ -282,18 +328,26 @@ __global__ __launch_bounds__(256) void randn_fill_kernel(float* out, int n, unsi
 
 // ------------------------------------------------------------------ K13
 // HISTORY (the three tail kernels): the multistep solvers' term c5 * (the PREVIOUS step's thresholded x0), coefficient column 5, and the
-// store of this step's thresholded x0 for the next one.  The history kernels take the extension struct as one more argument; the
-// <false> instantiations have the argument list -- and the instructions -- of the kernels before the template parameter existed.
+// store of this step's thresholded x0 for the next one.  The history kernels take the extension struct as one more argument.
+// INPAINT: the masked replace of the known region (known_step4) behind the step, before the store; one more argument, mi_inpaint_params, last.
+// The <false, false> instantiations have the argument list -- and the instructions -- of the kernels before the template parameters existed.
 __device__ __forceinline__ float* x0_prev_of() { return nullptr; }
 __device__ __forceinline__ float* x0_prev_of(const mi_sampler_ext_params& e) { return e.x0_prev; }
+__device__ __forceinline__ float* x0_prev_of(const mi_inpaint_params&) { return nullptr; }
+__device__ __forceinline__ float* x0_prev_of(const mi_sampler_ext_params& e, const mi_inpaint_params&) { return e.x0_prev; }
+__device__ __forceinline__ mi_inpaint_params known_of() { return {}; }
+__device__ __forceinline__ mi_inpaint_params known_of(const mi_sampler_ext_params&) { return {}; }
+__device__ __forceinline__ mi_inpaint_params known_of(const mi_inpaint_params& ip) { return ip; }
+__device__ __forceinline__ mi_inpaint_params known_of(const mi_sampler_ext_params&, const mi_inpaint_params& ip) { return ip; }
 
-template <bool HISTORY, typename... EXT>
+template <bool HISTORY, bool INPAINT, typename... EXT>
 __global__ __launch_bounds__(256) void posterior_kernel(const mi_posterior_params p, const EXT... ext) {
-    static_assert(sizeof...(EXT) == (HISTORY ? 1 : 0), "the history kernels take mi_sampler_ext_params");
+    static_assert(sizeof...(EXT) == (HISTORY ? 1 : 0) + (INPAINT ? 1 : 0), "the history kernels take mi_sampler_ext_params, the inpainting kernels mi_inpaint_params");
     const int b = blockIdx.y;
     const int t = *p.t_state - p.t_off;
     const step_coef cf = load_step_coef<HISTORY>(p.coef, t);
     float* const prev = x0_prev_of(ext...);
+    [[maybe_unused]] const mi_inpaint_params ip = known_of(ext...);
     const float s = threshold_scale(p.s_q[b]);
     const int k = (p.T - 1) - t;
     const int n = p.n, nq = (n + 3) / 4;
@@ -307,6 +361,7 @@ __global__ __launch_bounds__(256) void posterior_kernel(const mi_posterior_param
         if constexpr (HISTORY) ld_quad(prev + ob, 4 * qd, n, vec, pv);
 #pragma unroll
         for (int e = 0; e < 4; ++e) x[e] = posterior_elem<HISTORY>(x0[e], x[e], z[e], s, cf, pv[e]);      // (past the row's end: on zeros, not stored)
+        if constexpr (INPAINT) known_step4(ip, p, b, t, k, qd, n, vec, x);
         st_quad(p.x + ob, 4 * qd, n, vec, x);
         if constexpr (HISTORY) st_quad(prev + ob, 4 * qd, n, vec, pv);
     }
@@ -319,9 +374,9 @@ __global__ __launch_bounds__(256) void posterior_kernel(const mi_posterior_param
 #define SS_THREADS 1024
 #endif
 constexpr int SS_NT = SS_THREADS, SS_MAXQ = MI_SAMPLER_SMALL_N / 4 / SS_NT;      // quads per work-item
-template <bool HISTORY, typename... EXT>
+template <bool HISTORY, bool INPAINT, typename... EXT>
 __global__ __launch_bounds__(SS_NT) void sampler_small_kernel(const mi_cfg_x0_params c, const mi_quantile_params q, const mi_posterior_params pp, const EXT... ext) {
-    static_assert(sizeof...(EXT) == (HISTORY ? 1 : 0), "the history kernels take mi_sampler_ext_params");
+    static_assert(sizeof...(EXT) == (HISTORY ? 1 : 0) + (INPAINT ? 1 : 0), "the history kernels take mi_sampler_ext_params, the inpainting kernels mi_inpaint_params");
     __shared__ unsigned lh[2][MI_Q_BINS];
     __shared__ int scratch[8];
     __shared__ unsigned nan_sh;
@@ -329,6 +384,7 @@ __global__ __launch_bounds__(SS_NT) void sampler_small_kernel(const mi_cfg_x0_pa
     const int t = *c.t_state - c.t_off;
     const step_coef cf = load_step_coef<HISTORY>(c.coef, t);
     float* const prev = x0_prev_of(ext...);
+    [[maybe_unused]] const mi_inpaint_params ip = known_of(ext...);
     const bool vec = (n & 3) == 0;
     const size_t ob = (size_t)b * n, on = (size_t)(b + c.B) * n;
     float x0v[SS_MAXQ][4], xtv[SS_MAXQ][4];
@@ -399,6 +455,7 @@ __global__ __launch_bounds__(SS_NT) void sampler_small_kernel(const mi_cfg_x0_pa
         if constexpr (HISTORY) ld_quad(prev + ob, 4 * qd, n, vec, pv);
 #pragma unroll
         for (int e = 0; e < 4; ++e) r[e] = posterior_elem<HISTORY>(x0v[u][e], xtv[u][e], z[e], s, cf, pv[e]);
+        if constexpr (INPAINT) known_step4(ip, pp, b, t, k, qd, n, vec, r);
         st_quad(pp.x + ob, 4 * qd, n, vec, r);
         if constexpr (HISTORY) st_quad(prev + ob, 4 * qd, n, vec, pv);
     }
@@ -430,6 +487,35 @@ __global__ __launch_bounds__(256) void lowres_augment_kernel(const float* img, c
         if (noise) v = __fadd_rn(__fmul_rn(a, v), __fmul_rn(b, noise[i]));       // diffusion_model.py:142-147
         if (normalize) v = __fsub_rn(__fmul_rn(v, 2.0f), 1.0f);                  // helpers.py:105-110 via Imagen.py:393
         out[i] = v;
+    }
+}
+
+// blend 0 of an inpainting call, right behind the draw of x_T: x = m ? a*y + b*z'_0 : x (known_blend4 with j = 0)
+__global__ __launch_bounds__(256) void known_blend0_kernel(float* x, int B, int n, const mi_inpaint_params ip, float a, float bcoef, unsigned long long seed, int sample0) {
+    const int b = blockIdx.y, nq = (n + 3) / 4;
+    const bool vec = (n & 3) == 0;
+    for (int qd = blockIdx.x * 256 + threadIdx.x; qd < nq; qd += gridDim.x * 256) {
+        float v[4];
+        ld_quad(x + (size_t)b * n, 4 * qd, n, vec, v);
+        known_blend4(ip, seed, sample0, B, b, 0, qd, n, vec, a, bcoef, v);
+        st_quad(x + (size_t)b * n, 4 * qd, n, vec, v);
+    }
+}
+
+// the known image of a stage in the sampler's range: clamp to [0, 1] (NaN stays NaN, as torch.clamp), then *2-1 when `normalize`
+__global__ __launch_bounds__(256) void known_image_kernel(const float* img, float* out, long long total, int normalize) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        float v = img[i] != img[i] ? img[i] : fminf(fmaxf(img[i], 0.0f), 1.0f);
+        if (normalize) v = __fsub_rn(__fmul_rn(v, 2.0f), 1.0f);                  // helpers.py:105-110
+        out[i] = v;
+    }
+}
+// the mask at a stage's size: nearest neighbour, source index floor(i * Hin / size) (F.interpolate(mode='nearest')); nonzero -> 1
+__global__ __launch_bounds__(256) void known_mask_kernel(const unsigned char* in, unsigned char* out, int Hin, int Win, int size) {
+    const int b = blockIdx.y;
+    for (int o = blockIdx.x * 256 + threadIdx.x; o < size * size; o += gridDim.x * 256) {
+        const int sy = (int)(((long long)(o / size) * Hin) / size), sx = (int)(((long long)(o % size) * Win) / size);
+        out[(size_t)b * size * size + o] = in[((size_t)b * Hin + sy) * Win + sx] ? 1 : 0;
     }
 }
 
@@ -490,9 +576,9 @@ __host__ __device__ inline sg_layout sg_sync_layout(int B) {
     return l;
 }
 
-template <bool HISTORY, typename... EXT>
+template <bool HISTORY, bool INPAINT, typename... EXT>
 __global__ __launch_bounds__(SG_NT) void sampler_group_kernel(const mi_cfg_x0_params c, const mi_quantile_params q, const mi_posterior_params pp, char* sync, const int G, const EXT... ext) {
-    static_assert(sizeof...(EXT) == (HISTORY ? 1 : 0), "the history kernels take mi_sampler_ext_params");
+    static_assert(sizeof...(EXT) == (HISTORY ? 1 : 0) + (INPAINT ? 1 : 0), "the history kernels take mi_sampler_ext_params, the inpainting kernels mi_inpaint_params");
     __shared__ unsigned lh[2][MI_Q_BINS];
     __shared__ __attribute__((aligned(16))) unsigned hc[2][MI_Q_BINS];
     __shared__ int scratch[8];
@@ -526,6 +612,7 @@ __global__ __launch_bounds__(SG_NT) void sampler_group_kernel(const mi_cfg_x0_pa
     const int t = *c.t_state - c.t_off;
     const step_coef cf = load_step_coef<HISTORY>(c.coef, t);
     float* const prev = x0_prev_of(ext...);
+    [[maybe_unused]] const mi_inpaint_params ip = known_of(ext...);
     const size_t ob = (size_t)b * n, on = (size_t)(b + c.B) * n;
     const int q0 = g * SG_NT * SG_MAXQ;                        // this workgroup's quads: q0 + tid + u * SG_NT
     // fail-stop: this workgroup's part of the image becomes NaN (never a stale or half-finished x_t)
@@ -634,6 +721,7 @@ __global__ __launch_bounds__(SG_NT) void sampler_group_kernel(const mi_cfg_x0_pa
         if constexpr (HISTORY) ld_quad(prev + ob, 4 * qd, n, true, pv);
 #pragma unroll
         for (int e = 0; e < 4; ++e) r[e] = posterior_elem<HISTORY>(x0v[u][e], xtv[u][e], z[e], s, cf, pv[e]);
+        if constexpr (INPAINT) known_step4(ip, pp, b, t, k, qd, n, true, r);
         st_quad(pp.x + ob, 4 * qd, n, true, r);
         if constexpr (HISTORY) st_quad(prev + ob, 4 * qd, n, true, pv);
     }
@@ -673,19 +761,38 @@ static int check_step_params(const char* name, const mi_cfg_x0_params* c, const 
     return MI_OK;
 }
 
-static int sampler_step_small(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* stream) {
+// what the inpainting entries ask of their block (ip may be NULL: the entry is then its *_ext_fwd form)
+static int check_inpaint_params(const char* name, const mi_inpaint_params* ip, int n) {
+    if (!ip) return MI_OK;
+    if (!ip->known || !ip->mask) { mi_set_error("%s: inpaint block without known image / mask", name); return MI_ERR_INVALID; }
+    if (ip->hw <= 0 || n % ip->hw != 0) { mi_set_error("%s: inpaint block with hw = %d for n = %d (n must be a multiple of hw > 0)", name, ip->hw, n); return MI_ERR_INVALID; }
+    return MI_OK;
+}
+
+static int sampler_step_small(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e,
+                              const mi_inpaint_params* ip, void* stream) {
     if (const int rc = check_step_params("mi_sampler_step_small_fwd", c, q, pp)) return rc;
+    if (const int rc = check_inpaint_params("mi_sampler_step_small_inpaint_fwd", ip, c->n)) return rc;
     if (c->n > MI_SAMPLER_SMALL_N) { mi_set_error("mi_sampler_step_small_fwd: n = %d > %d", c->n, MI_SAMPLER_SMALL_N); return MI_ERR_UNSUPPORTED; }
-    if (e) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_small_kernel<true, mi_sampler_ext_params>), dim3(c->B), dim3(SS_NT), 0, (hipStream_t)stream, *c, *q, *pp, *e);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_small_kernel<false>), dim3(c->B), dim3(SS_NT), 0, (hipStream_t)stream, *c, *q, *pp);
+    const dim3 grid(c->B), wg(SS_NT);
+    hipStream_t st = (hipStream_t)stream;
+    if (e && ip) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_small_kernel<true, true, mi_sampler_ext_params, mi_inpaint_params>), grid, wg, 0, st, *c, *q, *pp, *e, *ip);
+    else if (ip) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_small_kernel<false, true, mi_inpaint_params>), grid, wg, 0, st, *c, *q, *pp, *ip);
+    else if (e) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_small_kernel<true, false, mi_sampler_ext_params>), grid, wg, 0, st, *c, *q, *pp, *e);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_small_kernel<false, false>), grid, wg, 0, st, *c, *q, *pp);
     return mi_check_launch("sampler_small_kernel");
 }
 extern "C" int mi_sampler_step_small_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, void* stream) {
-    return sampler_step_small(c, q, pp, nullptr, stream);
+    return sampler_step_small(c, q, pp, nullptr, nullptr, stream);
 }
 // the *_ext_fwd entries: with e->x0_prev the history kernels, without it (or without e) exactly the plain entries
 extern "C" int mi_sampler_step_small_ext_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* stream) {
-    return sampler_step_small(c, q, pp, (e && e->x0_prev) ? e : nullptr, stream);
+    return sampler_step_small(c, q, pp, (e && e->x0_prev) ? e : nullptr, nullptr, stream);
+}
+// the *_inpaint_fwd entries: the *_ext_fwd entry plus the masked replace of the known region; without ip exactly the *_ext_fwd entry
+extern "C" int mi_sampler_step_small_inpaint_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e,
+                                                 const mi_inpaint_params* ip, void* stream) {
+    return sampler_step_small(c, q, pp, (e && e->x0_prev) ? e : nullptr, ip, stream);
 }
 
 extern "C" int mi_sampler_group_size(int n) {
@@ -696,34 +803,69 @@ extern "C" int mi_sampler_group_size(int n) {
 extern "C" long long mi_sampler_group_sync_bytes(int B, int n) {
     return (B > 0 && mi_sampler_group_size(n) > 0) ? sg_sync_layout(B).total : 0;
 }
-static int sampler_step_group(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* sync, void* stream) {
+static int sampler_step_group(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e,
+                              const mi_inpaint_params* ip, void* sync, void* stream) {
     if (const int rc = check_step_params("mi_sampler_step_group_fwd", c, q, pp)) return rc;
+    if (const int rc = check_inpaint_params("mi_sampler_step_group_inpaint_fwd", ip, c->n)) return rc;
     const int G = mi_sampler_group_size(c->n);
     if (!G) { mi_set_error("mi_sampler_step_group_fwd: n = %d unsupported (a multiple of 4, at most %d)", c->n, 256 * SG_NT * SG_MAXQ * 4); return MI_ERR_UNSUPPORTED; }
     if (!sync) { mi_set_error("mi_sampler_step_group_fwd: sync buffer missing"); return MI_ERR_INVALID; }
-    if (e) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_group_kernel<true, mi_sampler_ext_params>), dim3(c->B * G), dim3(SG_NT), 0, (hipStream_t)stream, *c, *q, *pp, (char*)sync, G, *e);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_group_kernel<false>), dim3(c->B * G), dim3(SG_NT), 0, (hipStream_t)stream, *c, *q, *pp, (char*)sync, G);
+    const dim3 grid(c->B * G), wg(SG_NT);
+    hipStream_t st = (hipStream_t)stream;
+    if (e && ip) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_group_kernel<true, true, mi_sampler_ext_params, mi_inpaint_params>), grid, wg, 0, st, *c, *q, *pp, (char*)sync, G, *e, *ip);
+    else if (ip) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_group_kernel<false, true, mi_inpaint_params>), grid, wg, 0, st, *c, *q, *pp, (char*)sync, G, *ip);
+    else if (e) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_group_kernel<true, false, mi_sampler_ext_params>), grid, wg, 0, st, *c, *q, *pp, (char*)sync, G, *e);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_group_kernel<false, false>), grid, wg, 0, st, *c, *q, *pp, (char*)sync, G);
     return mi_check_launch("sampler_group_kernel");
 }
 extern "C" int mi_sampler_step_group_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, void* sync, void* stream) {
-    return sampler_step_group(c, q, pp, nullptr, sync, stream);
+    return sampler_step_group(c, q, pp, nullptr, nullptr, sync, stream);
 }
 extern "C" int mi_sampler_step_group_ext_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e, void* sync, void* stream) {
-    return sampler_step_group(c, q, pp, (e && e->x0_prev) ? e : nullptr, sync, stream);
+    return sampler_step_group(c, q, pp, (e && e->x0_prev) ? e : nullptr, nullptr, sync, stream);
+}
+extern "C" int mi_sampler_step_group_inpaint_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e,
+                                                 const mi_inpaint_params* ip, void* sync, void* stream) {
+    return sampler_step_group(c, q, pp, (e && e->x0_prev) ? e : nullptr, ip, sync, stream);
 }
 
-static int posterior_step(const char* name, const mi_posterior_params* p, const mi_sampler_ext_params* e, void* stream) {
+static int posterior_step(const char* name, const mi_posterior_params* p, const mi_sampler_ext_params* e, const mi_inpaint_params* ip, void* stream) {
     if (p->B <= 0 || p->n <= 0) { mi_set_error("%s: empty", name); return MI_ERR_INVALID; }
-    const dim3 grid(grid_for((p->n + 3) / 4, 256), p->B);
-    if (e) hipLaunchKernelGGL(HIP_KERNEL_NAME(posterior_kernel<true, mi_sampler_ext_params>), grid, dim3(256), 0, (hipStream_t)stream, *p, *e);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(posterior_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, *p);
+    if (const int rc = check_inpaint_params(name, ip, p->n)) return rc;
+    const dim3 grid(grid_for((p->n + 3) / 4, 256), p->B), wg(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (e && ip) hipLaunchKernelGGL(HIP_KERNEL_NAME(posterior_kernel<true, true, mi_sampler_ext_params, mi_inpaint_params>), grid, wg, 0, st, *p, *e, *ip);
+    else if (ip) hipLaunchKernelGGL(HIP_KERNEL_NAME(posterior_kernel<false, true, mi_inpaint_params>), grid, wg, 0, st, *p, *ip);
+    else if (e) hipLaunchKernelGGL(HIP_KERNEL_NAME(posterior_kernel<true, false, mi_sampler_ext_params>), grid, wg, 0, st, *p, *e);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(posterior_kernel<false, false>), grid, wg, 0, st, *p);
     return mi_check_launch("posterior_kernel");
 }
 extern "C" int mi_posterior_fwd(const mi_posterior_params* p, void* stream) {
-    return posterior_step("mi_posterior_fwd", p, nullptr, stream);
+    return posterior_step("mi_posterior_fwd", p, nullptr, nullptr, stream);
 }
 extern "C" int mi_posterior_ext_fwd(const mi_posterior_params* p, const mi_sampler_ext_params* e, void* stream) {
-    return (e && e->x0_prev) ? posterior_step("mi_posterior_ext_fwd", p, e, stream) : posterior_step("mi_posterior_fwd", p, nullptr, stream);
+    return (e && e->x0_prev) ? posterior_step("mi_posterior_ext_fwd", p, e, nullptr, stream) : posterior_step("mi_posterior_fwd", p, nullptr, nullptr, stream);
+}
+extern "C" int mi_posterior_inpaint_fwd(const mi_posterior_params* p, const mi_sampler_ext_params* e, const mi_inpaint_params* ip, void* stream) {
+    if (!ip) return mi_posterior_ext_fwd(p, e, stream);
+    return posterior_step("mi_posterior_inpaint_fwd", p, (e && e->x0_prev) ? e : nullptr, ip, stream);
+}
+
+// blend 0 and the per-stage preparation of an inpainting call
+extern "C" int mi_inpaint_blend0_fwd(float* x, int B, int n, const mi_inpaint_params* ip, float a, float b, uint64_t seed, int sample0, void* stream) {
+    if (!x || B <= 0 || n <= 0 || !ip) { mi_set_error("mi_inpaint_blend0_fwd: empty"); return MI_ERR_INVALID; }
+    if (const int rc = check_inpaint_params("mi_inpaint_blend0_fwd", ip, n)) return rc;
+    hipLaunchKernelGGL(known_blend0_kernel, dim3(grid_for((n + 3) / 4, 256), B), dim3(256), 0, (hipStream_t)stream, x, B, n, *ip, a, b, (unsigned long long)seed, sample0);
+    return mi_check_launch("known_blend0_kernel");
+}
+extern "C" int mi_inpaint_prepare_fwd(const float* img, float* known, int B, int n, int normalize, const unsigned char* mask_in, int Hin, int Win, unsigned char* mask_out,
+                                      int size, void* stream) {
+    if (!img || !known || !mask_in || !mask_out || B <= 0 || n <= 0 || Hin <= 0 || Win <= 0 || size <= 0 || n % (size * size) != 0) {
+        mi_set_error("mi_inpaint_prepare_fwd: bad params"); return MI_ERR_INVALID;
+    }
+    hipLaunchKernelGGL(known_image_kernel, dim3(grid_for((long long)B * n)), dim3(256), 0, (hipStream_t)stream, img, known, (long long)B * n, normalize);
+    hipLaunchKernelGGL(known_mask_kernel, dim3(grid_for((long long)size * size, 256), B), dim3(256), 0, (hipStream_t)stream, mask_in, mask_out, Hin, Win, size);
+    return mi_check_launch("known_image_kernel / known_mask_kernel");
 }
 
 // set: 0 advance by 1 | 1 set to value | 2 advance by value; `mapped`: the entries that take the step -> timestep map from e

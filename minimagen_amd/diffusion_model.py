@@ -52,9 +52,29 @@ class GaussianDiffusion(nn.Module):
         """diffusion_model.py:81-87"""
         return [torch.full((batch,), i, device=device, dtype=torch.long) for i in reversed(range(self.num_timesteps))]
 
-    def sampler_coef_table(self) -> torch.Tensor:
+    def _abar64(self) -> torch.Tensor:
+        """alphas_cumprod in fp64, from the betas as __init__ builds them"""
+        scale = 1000 / self.num_timesteps
+        betas = torch.linspace(scale * 0.0001, scale * 0.02, self.num_timesteps, dtype=torch.float64)
+        return torch.cumprod(1. - betas, dim=0)
+
+    @staticmethod
+    def _known_columns64(a: torch.Tensor) -> torch.Tensor:
+        """float64[S][2], the inpainting columns 6 and 7 of a coefficient table whose rows sit at abar = ``a``: sqrt(abar_{k-1}) and
+        sqrt(1 - abar_{k-1}) with abar_{-1} = 1 -- the level the known pixels are re-imposed at behind step k; row 0 is exactly (1, 0)"""
+        ap = F.pad(a[:-1], (1, 0), value=1.)
+        return torch.stack((torch.sqrt(ap), torch.sqrt(1. - ap)), dim=1)
+
+    def known_start_coefs(self):
+        """(a, b) = (sqrt(abar_{T-1}), sqrt(1 - abar_{T-1})) as fp32 values: the level of x_T, where the known region of an inpainting call
+        is imposed first (blend 0).  Every step count and sampler starts at the trained timestep T-1."""
+        a = self._abar64()[-1]
+        return float(torch.sqrt(a).to(torch.float32)), float(torch.sqrt(1. - a).to(torch.float32))
+
+    def sampler_coef_table(self, known: bool = False) -> torch.Tensor:
         """[T][8] table consumed by mi_cfg_x0_fwd / mi_posterior_fwd: per-timestep scalars gathered from the
-        buffers above; column 4 is [t != 0] * exp(0.5 * posterior_log_variance_clipped) (Imagen.py:364-370)."""
+        buffers above; column 4 is [t != 0] * exp(0.5 * posterior_log_variance_clipped) (Imagen.py:364-370).
+        ``known``: plus the inpainting columns 6 and 7 (fp64 from the betas, rounded once); without it they are zero."""
         T = self.num_timesteps
         tab = torch.zeros(T, 8, dtype=torch.float32)
         cpu = lambda v: v.detach().to('cpu', torch.float32)
@@ -65,6 +85,8 @@ class GaussianDiffusion(nn.Module):
         nonzero = torch.ones(T)
         nonzero[0] = 0.
         tab[:, 4] = nonzero * (0.5 * cpu(self.posterior_log_variance_clipped)).exp()
+        if known:
+            tab[:, 6:8] = self._known_columns64(self._abar64()).to(torch.float32)
         return tab
 
     # ---- sampling in S <= T steps over a subsequence of the trained timesteps (not in the reference; DESIGN.md "Fewer sampling steps")
@@ -77,7 +99,7 @@ class GaussianDiffusion(nn.Module):
             raise ValueError(f'sample_steps must be in [2, {T}] for a schedule of {T} timesteps, got {steps}')
         return torch.tensor([(2 * k * (T - 1) + (S - 1)) // (2 * (S - 1)) for k in range(S)], dtype=torch.int64)
 
-    def _sampler_tables64(self, steps: int, sampler: str = 'ddpm', eta: float = None):
+    def _sampler_tables64(self, steps: int, sampler: str = 'ddpm', eta: float = None, known: bool = False):
         """sampler_tables before the rounding to fp32: (tau int64[S], abar float64[S], coef float64[S][8])"""
         if sampler not in self.SAMPLERS:
             raise ValueError(f'sampler must be one of {self.SAMPLERS}, got {sampler!r}')
@@ -117,14 +139,18 @@ class GaussianDiffusion(nn.Module):
                     r = (lam[k] - lam[k + 1]) / h
                     tab[k, 2] = m * (1. + 1. / (2. * r))
                     tab[k, 5] = -m / (2. * r)
+        if known:
+            tab[:, 6:8] = self._known_columns64(a)
         return tau, a, tab
 
-    def sampler_tables(self, steps: int, sampler: str = 'ddpm', eta: float = None):
+    def sampler_tables(self, steps: int, sampler: str = 'ddpm', eta: float = None, known: bool = False):
         """(tau int64[S], coef float32[S][8]) for ``steps`` sampling steps over the trained timesteps tau: row k of ``coef`` is the step at
         timestep tau_k (the sampler walks k = S-1 .. 0).  With cN = column N (the naming of DESIGN.md section 14 and the C header): x0 = c0 x - c1 eps, then
         x' = c2 x0 + c3 x + c5 x0_prev + c4 z with the thresholded x0 of this and of the previous step.  'ddpm' is 'ddim' with eta = 1 (the reference's ancestral step when
-        S = T); 'dpmpp_2m' is deterministic.  Everything in fp64 from the betas, rounded to fp32 once."""
-        tau, _, tab = self._sampler_tables64(steps, sampler, eta)
+        S = T); 'dpmpp_2m' is deterministic.  Everything in fp64 from the betas, rounded to fp32 once.  ``known``: plus c6 = sqrt(abar_{tau_{k-1}}) and
+        c7 = sqrt(1 - abar_{tau_{k-1}}), the level an inpainting call re-imposes its known pixels at behind step k (row 0: exactly 1 and 0);
+        without it columns 6 and 7 are zero and the table is what it was before the flag existed."""
+        tau, _, tab = self._sampler_tables64(steps, sampler, eta, known)
         return tau, tab.to(torch.float32)
 
     # ---- the per-timestep helpers of the reference's public API (diffusion_model.py:89-162).  The sampling hot path has them fused

@@ -53,7 +53,9 @@ def sample_distributed(imagen, *, text_embeds: torch.Tensor, text_masks: Optiona
     """Every rank passes the SAME full-batch ``text_embeds``/``text_masks``; rank r samples rows shard_bounds(B, N, r)
     and (if ``gather``) all ranks return the full batch.  ``sample_kwargs`` go to ``Imagen.sample`` unchanged (``cond_scale``, ``_seed``,
     ``sample_steps`` / ``sampler`` / ``sampler_eta``, ...): the noise is keyed by the global row, the stage and the STEP index, so the
-    gathered batch equals the unsharded call bit for bit for every solver and step count."""
+    gathered batch equals the unsharded call bit for bit for every solver and step count.  The per-row pixel inputs ``inpaint_images`` /
+    ``inpaint_masks`` / ``start_image`` are passed full-batch as well and sharded by the same row bounds (the known-region draws are keyed
+    like the step noise); ``start_at_stage`` / ``stop_at_stage`` go through (the gathered images then have the last stage's size that ran)."""
     ws = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     batch = text_embeds.shape[0]
@@ -63,9 +65,12 @@ def sample_distributed(imagen, *, text_embeds: torch.Tensor, text_masks: Optiona
         # more ranks than samples: this rank has nothing to sample but must still take part in the collective (a rank that raised
         # or returned early would leave the others hanging in all_gather)
         dev = next(imagen.parameters()).device
-        size = imagen.image_sizes[-1]
+        size = imagen.image_sizes[(sample_kwargs.get("stop_at_stage") or len(imagen.image_sizes)) - 1]
         local = torch.zeros(0, imagen.channels, size, size, dtype=torch.float32, device=dev)
         return gather_samples(local, batch, group) if (gather and not _alone(ws)) else local
+    for name in ("inpaint_images", "inpaint_masks", "start_image"):
+        if sample_kwargs.get(name) is not None:
+            sample_kwargs[name] = sample_kwargs[name][lo:hi].contiguous()
     local = imagen.sample(text_embeds=text_embeds[lo:hi].contiguous(),
                           text_masks=None if text_masks is None else text_masks[lo:hi].contiguous(),
                           _sample_offset=seed_off + lo, **sample_kwargs)

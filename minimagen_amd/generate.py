@@ -81,7 +81,8 @@ def sample_and_save(captions: list, *, minimagen: Optional[Imagen] = None, train
     """generate.py:124-173: writes ``captions.txt`` (+ ``imagen_training_directory.txt``) into ``save_directory`` and
     ``generated_images/image_<caption index>.<filetype>``; exactly one of ``minimagen`` / ``training_directory``.
     ``sample_args`` goes to ``Imagen.sample`` as keywords -- ``cond_scale``, and the step-count knobs ``sample_steps`` / ``sampler`` /
-    ``sampler_eta`` (e.g. ``dict(cond_scale=3., sample_steps=25, sampler='dpmpp_2m')``) among them."""
+    ``sampler_eta`` (e.g. ``dict(cond_scale=3., sample_steps=25, sampler='dpmpp_2m')``) among them, and the pixel inputs ``inpaint_images`` /
+    ``inpaint_masks`` / ``start_image`` / ``start_at_stage`` / ``stop_at_stage`` (one row per caption)."""
     assert not (minimagen is None and training_directory is None), \
         "Must supply either a training directory or MinImagen instance."
     assert (minimagen is not None) ^ (training_directory is not None), \

@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib as L
-from .helpers import quantile_rank
+from .helpers import cubic_taps, quantile_rank
 
 def _drain(dev):
     if L.backend() == "hip-gfx950" and torch.cuda.is_available():
@@ -26,19 +26,48 @@ def destroy_graph(entry, dev):
         entry["graph"] = None
 
 
+def cubic_resize(ws, img, image_size: int, stream):
+    """``img`` [B, C, H, W] at the workspace's image size through mi_resize_fwd (helpers.cubic_taps: antialiased when shrinking); ``img`` itself
+    when the size already matches.  Tap tables: built and uploaded once per (workspace, source size) -- an upload from pageable host memory
+    per call would block the host behind the previous call still running on this stage's stream."""
+    B, Cc, Hin, Win = img.shape
+    if Hin == image_size:
+        return img
+    cache = ws.resize_tabs
+    if (Hin, Win) not in cache:
+        _, idx_h, w_h = cubic_taps(Hin, image_size)
+        _, idx_w, w_w = cubic_taps(Win, image_size)
+        cache[(Hin, Win)] = ([t.to(ws.dev) for t in (idx_h, w_h, idx_w, w_w)], idx_h.shape[1], idx_w.shape[1])
+    tabs, kh, kw = cache[(Hin, Win)]
+    up = torch.empty(B, Cc, image_size, image_size, dtype=torch.float32, device=ws.dev)
+    rp = L.MiResizeParams(B * Cc, Hin, Win, image_size, image_size, kh, kw, L.ptr(img), L.ptr(up),
+                          L.ptr(tabs[0]), L.ptr(tabs[1]), L.ptr(tabs[2]), L.ptr(tabs[3]))
+    L.check(L.lib().mi_resize_fwd(C.byref(rp), stream), "mi_resize_fwd")
+    ws.resize_keepalive = tabs
+    return up
+
+
 class StageState:
     """One stage's loop state, kept on its workspace (so it dies with the buffers it points into) per schedule -- or per (schedule, S,
     sampler, eta) for a call with ``solver`` = (S, sampler, eta).  Every field is a slot; ``ext`` and ``group_sync`` stay UNSET until they exist
-    (``hasattr`` is how callers ask for a solver extension / a grouped tail); ``t_map`` / ``group_err_host``, None until then, answer the same here."""
+    (``hasattr`` is how callers ask for a solver extension / a grouped tail); ``t_map`` / ``group_err_host``, None until then, answer the same here.
+    ``hw`` (pixels per channel plane) makes it the state of an INPAINTING call -- an entry of its own: the coefficient table with columns 6 and
+    7, and the known-image / mask buffers every call copies into (so one captured graph serves every later call's images and masks);
+    ``ip`` (None otherwise) is the kernels' block over them, rebuilt by every stage_begin."""
     __slots__ = ("coef", "tau", "t_map", "x0_prev", "ext", "t_state", "x0", "hist", "s_q", "v_q", "seed_dev", "graphs",
-                 "group_sync", "group_err_host", "group_failed", "group_heal")
+                 "group_sync", "group_err_host", "group_failed", "group_heal", "known", "mask", "ip", "known_noise")
 
-    def __init__(self, sched, B: int, n: int, dev, solver=None):
+    def __init__(self, sched, B: int, n: int, dev, solver=None, hw: int = None):
         self.tau = self.t_map = self.x0_prev = None     # the reference's loop has no step -> timestep map and no history
+        self.known = self.mask = self.ip = self.known_noise = None
+        known = {} if hw is None else dict(known=True)
+        if hw is not None:
+            self.known = torch.zeros(B, n, dtype=torch.float32, device=dev)
+            self.mask = torch.zeros(B, hw, dtype=torch.uint8, device=dev)
         if solver is None:
-            self.coef = sched.sampler_coef_table().to(dev).contiguous()
+            self.coef = sched.sampler_coef_table(**known).to(dev).contiguous()
         else:
-            self.tau, coef = sched.sampler_tables(solver[0], solver[1], solver[2] if solver[1] == 'ddim' else None)
+            self.tau, coef = sched.sampler_tables(solver[0], solver[1], solver[2] if solver[1] == 'ddim' else None, **known)
             self.coef = coef.to(dev).contiguous()
             self.t_map = self.tau.to(torch.int32).to(dev).contiguous()
             if solver[1] == 'dpmpp_2m':
@@ -62,14 +91,18 @@ class StageState:
         self.graphs.clear()
 
 
-def stage_state(ws, sched, B: int, n: int, solver=None, eng=None, max_states: int = 8) -> StageState:
-    """The workspace's state for this schedule / solver setting, keyed by T for the default call and (T, S, sampler, eta) otherwise."""
+def stage_state(ws, sched, B: int, n: int, solver=None, eng=None, max_states: int = 8, hw: int = None) -> StageState:
+    """The workspace's state for this schedule / solver setting, keyed by T for the default call and (T, S, sampler, eta) otherwise; an
+    inpainting call (``hw``) has its own: that key plus an 'inpaint' marker, bounded together with the solver states."""
     store = ws.sampler_state
     key = sched.num_timesteps if solver is None else (sched.num_timesteps,) + tuple(solver)
+    if hw is not None:
+        key = (key if isinstance(key, tuple) else (key,)) + ("inpaint",)
+    bounded = isinstance(key, tuple)
     st = store.get(key)
-    if st is not None and solver is not None:
+    if st is not None and bounded:
         store[key] = store.pop(key)                      # most recently used last
-    if st is None and solver is not None:
+    if st is None and bounded:
         # bounded: a caller sweeping S or eta must not grow device memory (a status word still to be polled keeps its state object alive)
         solver_keys = [k for k in store if isinstance(k, tuple)]
         while len(solver_keys) >= max_states:
@@ -78,24 +111,48 @@ def stage_state(ws, sched, B: int, n: int, solver=None, eng=None, max_states: in
             if eng is not None:
                 eng.drop_step_tables(ws, old.t_state)
     if st is None:
-        st = store[key] = StageState(sched, B, n, ws.dev, solver)
+        st = store[key] = StageState(sched, B, n, ws.dev, solver, hw)
     return st
 
 
-def stage_begin(unet, shape, *, noise_scheduler, ws, noise_fn=None, seed: int = 0, sample0: int = 0, stage: int = 0, solver=None, max_states: int = 8):
+def known_begin(st: StageState, ws, shape, inpaint, *, sched, known_noise, seed: int, sample0: int, stage: int, stream):
+    """The known region of an inpainting call at this stage: the caller's images resized to the stage's size (cubic taps), clamped to [0, 1]
+    and normalised INTO st.known, the masks resized (nearest) into st.mask, and blend 0 on the x_T just drawn: the known pixels at the noise
+    level of x_T.  ``inpaint`` = (images float32 [B, C, H, W], masks uint8 [B, Hm, Wm], normalize), on the device."""
+    lib = L.lib()
+    images, masks, normalize = inpaint
+    B, Cc, H, W = shape
+    n = Cc * H * W
+    at_size = cubic_resize(ws, images, H, stream)
+    L.check(lib.mi_inpaint_prepare_fwd(L.ptr(at_size), L.ptr(st.known), B, n, 1 if normalize else 0, L.ptr(masks), masks.shape[1], masks.shape[2],
+                                       L.ptr(st.mask), H, stream), "mi_inpaint_prepare_fwd")
+    st.known_noise = known_noise          # (st.ip holds its address: an injected buffer lives until the next call's)
+    st.ip = L.MiInpaintParams(L.ptr(st.known), L.ptr(st.mask), H * W, (stage << 20) | (3 << 18), L.ptr(known_noise))
+    a, b = sched.known_start_coefs()
+    L.check(lib.mi_inpaint_blend0_fwd(L.ptr(ws.x), B, n, C.byref(st.ip), a, b, int(seed) & 0x7FFFFFFFFFFFFFFF, sample0, stream), "mi_inpaint_blend0_fwd")
+
+
+def stage_begin(unet, shape, *, noise_scheduler, ws, noise_fn=None, seed: int = 0, sample0: int = 0, stage: int = 0, solver=None, max_states: int = 8,
+                inpaint=None):
     """Everything of a stage's loop that does not depend on the PREVIOUS stage's image: x_T (Imagen.py:400), the device-resident timestep, the
-    per-step conditioning tables of all T steps.  sample() issues it for every stage before the first stage's loop, so that a later stage's
-    stream has it done while it waits for its low-resolution input (on-device noise only: injected noise is drawn in the reference's order)."""
+    per-step conditioning tables of all T steps -- and, for an inpainting call (``inpaint``: see known_begin), the stage's known image and mask
+    and blend 0.  sample() issues it for every stage before the first stage's loop, so that a later stage's
+    stream has it done while it waits for its low-resolution input (on-device noise only: injected noise is drawn in the reference's order,
+    then the T known-region draws)."""
     lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
     B, n = shape[0], shape[1] * shape[2] * shape[3]
     T = noise_scheduler.num_timesteps if solver is None else solver[0]        # steps of the loop (one draw each, for every solver)
-    st = stage_state(ws, noise_scheduler, B, n, solver, eng, max_states)
-    noise_dev = None
+    st = stage_state(ws, noise_scheduler, B, n, solver, eng, max_states, hw=None if inpaint is None else shape[2] * shape[3])
+    noise_dev = known_noise = None
     if noise_fn is not None:
         ws.x.copy_(noise_fn(shape))                                          # Imagen.py:400
         noise_dev = torch.stack([noise_fn(shape) for _ in range(T)]).to(ws.dev).contiguous()   # Imagen.py:361, in step order
+        if inpaint is not None:
+            known_noise = torch.stack([noise_fn(shape) for _ in range(T)]).to(ws.dev).contiguous()   # blends 0 .. T-1
     else:
         L.check(lib.mi_randn_fill(L.ptr(ws.x), B, n, seed, sample0, (stage << 20) | (1 << 19) | 1, stream), "mi_randn_fill")
+    if inpaint is not None:
+        known_begin(st, ws, shape, inpaint, sched=noise_scheduler, known_noise=known_noise, seed=seed, sample0=sample0, stage=stage, stream=stream)
     if st.t_map is None:
         L.check(lib.mi_step_set(L.ptr(st.t_state), L.ptr(ws.times), B, T - 1, stream), "mi_step_set")
     else:
@@ -110,10 +167,13 @@ def stage_begin(unet, shape, *, noise_scheduler, ws, noise_fn=None, seed: int = 
 def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream):
     """What follows the U-Net evaluation in a step, fixed once per graph entry -> (launch, advance): ``launch(k)`` enqueues the tail kernels of
     step *t_state - k (``kind``: "small" one workgroup per image | "group" cooperating workgroups | "separate" kernels), ``advance(n)`` moves the
-    device-resident step by n (mapped entries when the state has a step -> timestep map).  Always the *_ext_fwd tails: without st.ext / a history buffer they ARE the plain ones."""
+    device-resident step by n (mapped entries when the state has a step -> timestep map).  Always the *_ext_fwd tails: without st.ext / a history buffer they ARE the plain ones;
+    the *_inpaint_fwd tails for the state of an inpainting call (chosen here, once: a step has no branch for it)."""
     lib, tails = L.lib(), {}
     ext, q_ = (C.byref(st.ext) if st.t_map is not None else None), C.byref(qp)
     state = (L.ptr(st.t_state), L.ptr(ws.times), cp.B)
+    form, blocks = ("ext", (ext,)) if st.ip is None else ("inpaint", (ext, C.byref(st.ip)))
+    small_fwd, group_fwd, posterior_fwd = (getattr(lib, f"mi_{name}_{form}_fwd") for name in ("sampler_step_small", "sampler_step_group", "posterior"))
 
     def params(k):
         if k not in tails:
@@ -125,16 +185,16 @@ def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream):
         return tails[k]
 
     def small(k=0):
-        L.check(lib.mi_sampler_step_small_ext_fwd(*params(k), ext, stream), "mi_sampler_step_small_ext_fwd")
+        L.check(small_fwd(*params(k), *blocks, stream), f"mi_sampler_step_small_{form}_fwd")
 
     def group(k=0):
-        L.check(lib.mi_sampler_step_group_ext_fwd(*params(k), ext, L.ptr(st.group_sync), stream), "mi_sampler_step_group_ext_fwd")
+        L.check(group_fwd(*params(k), *blocks, L.ptr(st.group_sync), stream), f"mi_sampler_step_group_{form}_fwd")
 
     def separate(k=0):
         c_, _, p_ = params(k)
         L.check(lib.mi_cfg_x0_fwd(c_, stream), "mi_cfg_x0_fwd")
         L.check(lib.mi_quantile_fwd(q_, stream), "mi_quantile_fwd")
-        L.check(lib.mi_posterior_ext_fwd(p_, ext, stream), "mi_posterior_ext_fwd")
+        L.check(posterior_fwd(p_, *blocks, stream), f"mi_posterior_{form}_fwd")
 
     if st.t_map is None:
         advance = lambda n=1: L.check(lib.mi_step_advance_by(*state, n, stream), "mi_step_advance_by")
@@ -144,7 +204,7 @@ def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream):
 
 
 def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, noise_fn=None, seed: int = 0, sample0: int = 0,
-                  stage: int = 0, use_graph: bool = True, begun=None, solver=None, group_max: int = 8, max_states: int = 8):
+                  stage: int = 0, use_graph: bool = True, begun=None, solver=None, group_max: int = 8, max_states: int = 8, inpaint=None):
     """Imagen.py:373-420 + :329-370 + :261-326: T replays of [U-Net (both guidance halves) -> CFG combine + x0 -> dynamic-threshold quantile ->
     posterior draw -> t -= 1].  ``solver`` = (S, sampler, eta): S steps over a subsequence of the trained timesteps; the loop, the noise index and the
     Philox stream count STEPS: the reference's loop with T = S but for the state's step -> timestep map and history buffer (``st.ext``)."""
@@ -154,7 +214,8 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
     T = noise_scheduler.num_timesteps if solver is None else solver[0]
     two = ws.B2 != ws.B
     if begun is None:
-        begun = stage_begin(unet, shape, noise_scheduler=noise_scheduler, ws=ws, noise_fn=noise_fn, seed=seed, sample0=sample0, stage=stage, solver=solver, max_states=max_states)
+        begun = stage_begin(unet, shape, noise_scheduler=noise_scheduler, ws=ws, noise_fn=noise_fn, seed=seed, sample0=sample0, stage=stage, solver=solver, max_states=max_states,
+                            inpaint=inpaint)
     st, noise_dev = begun
     k_lo, k_hi, w = quantile_rank(n, im.dynamic_thresholding_percentile)
     # the whole tail in one launch: of one workgroup per image (n <= MI_SAMPLER_SMALL_N), or of <= group_max (0: never) cooperating workgroups -- but
@@ -167,7 +228,7 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
         st.group_sync.zero_()               # stream-ordered behind every launch queued on this lane: ticket, counters, histograms, error word
         st.group_heal = False
     # the captured graph of `per` steps is cached per (workspace, guidance, threshold, noise mode, shard offset, tail kind); the seed is in device memory
-    gkey = (float(cond_scale), two, k_lo, k_hi, w, sample0, stage, T, noise_dev is None, group) + (() if solver is None else (tuple(solver),))
+    gkey = (float(cond_scale), two, k_lo, k_hi, w, sample0, stage, T, noise_dev is None, group) + (() if solver is None else (tuple(solver),)) + (() if st.ip is None else ("inpaint",))
     entry = st.graphs.get(gkey) if (use_graph and noise_dev is None) else None
     seed = int(seed) & 0x7FFFFFFFFFFFFFFF
     if noise_dev is None:
