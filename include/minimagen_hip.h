@@ -148,6 +148,33 @@ typedef struct mi_crossembed_params {
 } mi_crossembed_params;
 int mi_crossembed_fwd(const mi_crossembed_params* p, void* stream);
 
+/* ---- K3 + the first Downsample of a memory_efficient U-Net (Unet.py:400, 415-416) as ONE launch: init_conv -> pre_downsample are both
+ * linear with only the Downsample's zero padding in between, so their composition is an 18 x 18, stride-2, pad-8 convolution from the
+ * image straight to the half-resolution tensor (packing.compose_init_down: nine border variants make it exact; pack_init_down_mfma).
+ * The full-resolution intermediate is never written.  One input half per launch, as with the matrix-core CrossEmbed: the other half
+ * (the step-invariant low-res conditioning image) is computed once by the same entry and comes back through `addend`.
+ * fp32 only; 8 Downsample output channels; C0 <= 4; H, W >= 4 and even, W % 4 == 0; anything else is MI_ERR_UNSUPPORTED.
+ * Struct index 26 of mi_struct_size; added within ABI 12 (no existing struct or entry changed). */
+typedef struct mi_init_down_params {
+    int B, H, W;                   /* INPUT resolution: out is [B][Cout][H/2][W/2] */
+    const float* in0; int C0;      /* the image half that is convolved */
+    const float* in1; int C1;      /* as in mi_crossembed_params; must be NULL / 0 (the second half goes through `addend`) */
+    int in0_batch_mod;             /* in0 is indexed by (b % in0_batch_mod); 0 = B */
+    int n_kernels;                 /* the CrossEmbed that was composed: <= 3 kernels, */
+    int ksize[3];                  /*   odd sizes <= 15, */
+    int cout[3];                   /*   <= 16 channels in all (they are summed out by the composition) */
+    int Cout;                      /* Downsample output channels: 8 */
+    const void* w_tab;             /* pack_init_down_mfma: [55 rows][5 steps][hi | lo][8][4][8] fp16 */
+    int w_exp;                     /* the power of two the table was pre-scaled by */
+    const float* bias9;            /* [3 vy][3 vx][Cout] composed bias per border variant, or NULL */
+    float* out; double* out_stats; /* [B][Cout][H/2][W/2], [B][Cout][nt][2] with nt = mi_init_down_tiles(tile_cfg, H, W) (or NULL) */
+    int out_st;                    /* storage of out / addend as mi_act.st: 0 (fp32) only */
+    int tile_cfg;                  /* output tile: 0 = 8 x 64, 1 = 8 x 32 */
+    const float* addend;           /* [B][Cout][H/2][W/2] added to the result, or NULL */
+} mi_init_down_params;
+int mi_init_down_tiles(int tile_cfg, int H, int W);   /* statistics tiles per image (depends on the image size only), < 0: bad arguments */
+int mi_init_down_fwd(const mi_init_down_params* p, void* stream);
+
 /* ---- conditioning --------------------------------------------------------------------- */
 typedef struct mi_linear {   /* torch nn.Linear layout: w[out][in], b[out] (b may be NULL) */
     const float* w; const float* b; int in, out;

@@ -50,6 +50,16 @@ class MiCrossEmbedParams(C.Structure):
     ]
 
 
+class MiInitDownParams(C.Structure):
+    _fields_ = [
+        ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
+        ("in0", C.c_void_p), ("C0", C.c_int), ("in1", C.c_void_p), ("C1", C.c_int),
+        ("in0_batch_mod", C.c_int), ("n_kernels", C.c_int), ("ksize", C.c_int * 3), ("cout", C.c_int * 3), ("Cout", C.c_int),
+        ("w_tab", C.c_void_p), ("w_exp", C.c_int), ("bias9", C.c_void_p),
+        ("out", C.c_void_p), ("out_stats", C.c_void_p), ("out_st", C.c_int), ("tile_cfg", C.c_int), ("addend", C.c_void_p),
+    ]
+
+
 class MiLinear(C.Structure):
     _fields_ = [("w", C.c_void_p), ("b", C.c_void_p), ("in_", C.c_int), ("out", C.c_int)]
 
@@ -201,7 +211,7 @@ class MiPackConv3Desc(C.Structure):
 _STRUCTS = {0: MiAct, 1: MiConvParams, 2: MiCrossEmbedParams, 3: MiLinear, 4: MiTextCondParams, 5: MiCondStepParams,
             6: MiAttnFoldParams, 7: MiCrossAttnParams, 8: MiCfgX0Params, 9: MiQuantileParams, 10: MiPosteriorParams,
             11: MiResizeParams, 12: MiSelfAttnParams, 13: MiChanFFParams, 14: MiFlashAttnParams, 15: MiTokensToNchwParams, 16: MiConvWgradParams, 17: MiBlockBwdParams, 18: MiCrossEmbedWgradParams, 19: MiFoldedAttnParams, 20: MiAdamTensor, 21: MiAdamParams, 22: MiPackConv3Desc,
-            23: MiFlashAttnTrainParams, 24: MiSamplerExtParams, 25: MiInpaintParams}
+            23: MiFlashAttnTrainParams, 24: MiSamplerExtParams, 25: MiInpaintParams, 26: MiInitDownParams}
 
 _lib = None
 _backend = None
@@ -220,7 +230,7 @@ def _bind(lib):
     for name in ("mi_conv_fwd", "mi_gn_coef_fwd", "mi_crossembed_fwd", "mi_text_cond_fwd", "mi_cond_step_fwd", "mi_attn_fold_rows", "mi_cross_attn_fwd",
                  "mi_cfg_x0_fwd", "mi_quantile_fwd", "mi_posterior_fwd", "mi_resize_fwd", "mi_self_attn_fwd", "mi_chan_ff_fwd",
                  "mi_flash_attn_fwd", "mi_conv_prep_fwd", "mi_tokens_to_nchw_fwd", "mi_conv_wgrad", "mi_block_bwd", "mi_crossembed_wgrad", "mi_folded_attn_fwd", "mi_folded_attn_bwd", "mi_adam_step",
-                 "mi_flash_attn_train_fwd", "mi_flash_attn_train_bwd"):
+                 "mi_flash_attn_train_fwd", "mi_flash_attn_train_bwd", "mi_init_down_fwd"):
         getattr(lib, name).argtypes = [vp, vp]
         getattr(lib, name).restype = i32
     lib.mi_conv_prep_bytes.argtypes = [i32, i32, i32, i32, i32]
@@ -269,6 +279,8 @@ def _bind(lib):
     lib.mi_conv_stripe_rows.argtypes = [vp]
     lib.mi_conv_stripe_rows.restype = i32
     lib.mi_conv_cout_tile.argtypes = [i32]
+    lib.mi_init_down_tiles.argtypes = [i32, i32, i32]
+    lib.mi_init_down_tiles.restype = i32
     lib.mi_conv_wgrad_workspace.argtypes = [i32, i32, i32]
     lib.mi_conv_wgrad_workspace.restype = C.c_longlong
     lib.mi_crossembed_wgrad_workspace.argtypes = [i32, i32, i32]

@@ -52,6 +52,7 @@ extern "C" int mi_struct_size(int which) {
         case 23: return (int)sizeof(mi_flash_attn_train_params);
         case 24: return (int)sizeof(mi_sampler_ext_params);
         case 25: return (int)sizeof(mi_inpaint_params);
+        case 26: return (int)sizeof(mi_init_down_params);
     }
     return -1;
 }

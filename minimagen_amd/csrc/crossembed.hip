@@ -459,6 +459,252 @@ __global__ __launch_bounds__(256, 2) void crossembed_mfma_kernel(const mi_crosse
     CE_TEND();
 }
 
+// ---- CrossEmbed o Downsample (Conv2d k4 s2 p1) as ONE 18 x 18 stride-2 pad-8 convolution on the matrix cores (mi_init_down_fwd) ----
+// Both layers are linear and nothing else reads the full-resolution tensor between them (memory_efficient U-Nets: Unet.py:400, 415-416), so
+// the composed weights (packing.compose_init_down) take the image straight to the half-resolution tensor.  Same scheme as
+// crossembed_mfma_kernel: the window is staged once, scaled by a per-workgroup power of two, split into fp16 hi / lo planes in LDS, and
+//   D[px m][(co, dy)] += A[m][(r; lg, dx, ci)] . B[(r; lg, dx, ci)][(co, dy)]        r = window row of the wave's output row PAIR (20 rows)
+//   A = act[row r][column 2 m + 8 s + 2 lg + dx][ci]   (pixel stride 2: the two taps of a lane are an even / odd column pair, 16 bytes)
+//   B = W'[vy][co][ci][ty = r - 2 dy][tx = 8 s + 2 lg + dx], one table row per (vy, ty): every lane reads its own row, so the vertical border
+//       variant (the reference zero-pads the INTERMEDIATE: the first / last output row leaves one Downsample tap out) is a row select.
+// The horizontal variant belongs to the output PIXEL (the M side), so it is a fourth / fifth K = 32 step whose A operand is the image's
+// first / last eight columns for the lane of output column 0 / Wo - 1 and a zero chunk for every other lane, against the table's
+// (border variant - interior) taps; corners come out right because those steps select their row by vy as well.  The table (280 KB) is read
+// from global memory (L2), one window row ahead; the A fragments come from LDS.  Wave w owns output rows 2 w, 2 w + 1 of the 8-row tile and
+// GX groups of 16 pixels, which share every B fragment.  All MFMAs of an accumulator have one shape (attention.hip:19-26).
+template <int GX>
+__global__ __launch_bounds__(256, 2) void init_down_mfma_kernel(const mi_init_down_params p, const uint4* __restrict__ wtab, const float* __restrict__ bias9) {
+    constexpr int TWO = 16 * GX;                                          // output tile: 8 rows x TWO columns
+    constexpr int IH = 32, PW = 2 * TWO + 24, NW4 = PW / 4, NU = IH * NW4, PER = (NU + 255) / 256;
+    constexpr int ZERO = IH * PW;                                         // 16 bytes of zeros behind each plane
+    constexpr int ROWQ = 5 * 2 * 32;                                      // table row pitch in 16-byte chunks: [step 5][hi | lo][co 8][lg 4]
+    __shared__ __attribute__((aligned(16))) uint2 actH[IH * PW + 2];
+    __shared__ __attribute__((aligned(16))) uint2 actL[IH * PW + 2];
+    __shared__ double red[4][16];
+    __shared__ float smax[4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lq = lane & 15, lg = lane >> 4;
+    const int H = p.H, W = p.W, HW = H * W, Ho = H >> 1, Wo = W >> 1;
+    const int tiles_x = (Wo + TWO - 1) / TWO, tile = blockIdx.x;
+    const int oy0 = (tile / tiles_x) * 8, ox0 = (tile % tiles_x) * TWO;
+    const int iy0 = 2 * oy0 - 8, ix0 = 2 * ox0 - 8;
+    const int b = blockIdx.y, Cin = p.C0;
+    const int b0 = p.in0_batch_mod > 0 ? b % p.in0_batch_mod : b;
+    const float* src = p.in0 + (size_t)b0 * Cin * HW;
+    const bool vec4 = (Wo & 3) == 0;                                      // else (Wo % 4 == 2) the output rows are only 8-byte aligned: element accesses
+
+    CE_TSTART();
+    // ---- stage the 32 x (2 TWO + 24) window: one unit = 4 pixels x all channels
+    float4 raw[PER][4];
+    unsigned inm = 0;
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int q = tid + u * 256, iy = q / NW4, xq = q - iy * NW4;
+        const int gy = iy0 + iy, gx = ix0 + 4 * xq;
+        const bool in = q < NU && gy >= 0 && gy < H && gx >= 0 && gx < W;          // W % 4 == 0: a float4 is inside or outside as a whole
+        inm |= in ? (1u << u) : 0u;
+        const int off = in ? gy * W + gx : 0;
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) raw[u][ci] = ci < Cin ? mi_ldg4(src + (size_t)ci * HW + off) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const int co = lq >> 1, dy = lq & 1;
+    const int oy = oy0 + 2 * wave + dy;
+    const int vy = oy == 0 ? 0 : (oy == Ho - 1 ? 2 : 1);
+    // the addend (the step-invariant low-res half) is requested now and consumed in the epilogue
+    float4 addv[GX];
+    if (p.addend) {
+#pragma unroll
+        for (int g = 0; g < GX; ++g) {
+            const int ox = ox0 + 16 * g + 4 * lg;
+            const size_t o = ((size_t)(b * 8 + co) * Ho + (oy < Ho ? oy : 0)) * Wo;
+            if (vec4) addv[g] = mi_ldg4(p.addend + o + (oy < Ho && ox < Wo ? ox : 0));
+            else {
+                float a[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a[j] = mi_ldg(p.addend + o + (oy < Ho && ox + j < Wo ? ox + j : 0));
+                addv[g] = make_float4(a[0], a[1], a[2], a[3]);
+            }
+        }
+    }
+    if (tid == 0) { actH[ZERO] = actH[ZERO + 1] = make_uint2(0u, 0u); actL[ZERO] = actL[ZERO + 1] = make_uint2(0u, 0u); }
+    CE_TPHASE(0);
+    float m = 0.0f;
+#pragma unroll
+    for (int u = 0; u < PER; ++u)
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) {
+            const float4 v = raw[u][ci];
+            const float a = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
+            m = ((inm >> u) & 1u) ? fmaxf(m, a) : m;
+        }
+    m = mi_wave_max(m);
+    if (lane == 0) smax[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
+    int ex = 0;                                     // max |x| 2^ex in [128, 256); no scaling for an all-zero or non-finite tile
+    {
+        const int be = (int)((__float_as_uint(m) & 0x7fffffffu) >> 23);
+        if (be != 0 && be != 255) ex = 8 - (be - 126);
+    }
+    const float sc = ldexpf(1.0f, ex);
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int q = tid + u * 256, iy = q / NW4, xq = q - iy * NW4;
+        if (q >= NU) continue;
+        const bool in = (inm >> u) & 1u;
+        uint2 hh[4], ll[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float y[4];
+#pragma unroll
+            for (int ci = 0; ci < 4; ++ci) {
+                const float4 v = raw[u][ci];
+                const float x = j == 0 ? v.x : (j == 1 ? v.y : (j == 2 ? v.z : v.w));
+                y[ci] = in ? x * sc : 0.0f;                                              // zero padding of the conv
+            }
+            mi_f16x4 h4, l4;
+            mi_split_f16(y, h4, l4);
+            hh[j] = __builtin_bit_cast(uint2, h4);
+            ll[j] = __builtin_bit_cast(uint2, l4);
+        }
+        const int d = iy * PW + 4 * xq;
+        *reinterpret_cast<uint4*>(&actH[d]) = make_uint4(hh[0].x, hh[0].y, hh[1].x, hh[1].y);
+        *reinterpret_cast<uint4*>(&actH[d + 2]) = make_uint4(hh[2].x, hh[2].y, hh[3].x, hh[3].y);
+        *reinterpret_cast<uint4*>(&actL[d]) = make_uint4(ll[0].x, ll[0].y, ll[1].x, ll[1].y);
+        *reinterpret_cast<uint4*>(&actL[d + 2]) = make_uint4(ll[2].x, ll[2].y, ll[3].x, ll[3].y);
+    }
+    __syncthreads();
+    CE_TPHASE(1);
+
+    // ---- the GEMM: per window row three K = 32 steps (24 horizontal taps, 18 live) for every group, + one for the group that holds output
+    // column 0 / Wo - 1.  The B fragments of row r + 1 are requested while row r is multiplied (two register sets, rows walked in pairs).
+    const bool hasL = ox0 == 0, hasR = ox0 + TWO >= Wo;                  // (workgroup-uniform)
+    const int xr = Wo - 1 - ox0, gR = xr >> 4;                            // the last output column within the tile (when hasR)
+    f32x4 acc[GX], accL = (f32x4){0.f, 0.f, 0.f, 0.f}, accR = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int g = 0; g < GX; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const uint4* const bbase = wtab + co * 4 + lg;
+    const int a0 = 4 * wave * PW + 2 * lq + 2 * lg;                        // + r PW + 32 g + 8 s
+    const int aL = lq == 0 ? 4 * wave * PW + 8 + 2 * lg : -1;             // image columns 2 lg, 2 lg + 1 (ox0 == 0)
+    const int aR = lq == (xr & 15) ? 4 * wave * PW + (W - 2 * ox0) + 2 * lg : -1;      // image columns W - 8 + 2 lg, + 1
+    struct BRow { uint4 v[5][2]; };
+    struct ARegs { ce_f16x8 h[GX], l[GX]; };
+    auto load_row = [&](int r, BRow& o) {
+        const int ty = r - 2 * dy;
+        const uint4* bp = bbase + ((unsigned)ty < 18u ? vy * 18 + ty : 54) * ROWQ;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) { o.v[s][0] = mi_ldg4u(bp + s * 64); o.v[s][1] = mi_ldg4u(bp + s * 64 + 32); }
+        if (hasL) { o.v[3][0] = mi_ldg4u(bp + 3 * 64); o.v[3][1] = mi_ldg4u(bp + 3 * 64 + 32); }
+        if (hasR) { o.v[4][0] = mi_ldg4u(bp + 4 * 64); o.v[4][1] = mi_ldg4u(bp + 4 * 64 + 32); }
+    };
+    auto load_a = [&](int r, int s, ARegs& a) {
+#pragma unroll
+        for (int g = 0; g < GX; ++g) {
+            const int idx = a0 + r * PW + 32 * g + 8 * s;
+            a.h[g] = __builtin_bit_cast(ce_f16x8, *reinterpret_cast<const uint4*>(&actH[idx]));
+            a.l[g] = __builtin_bit_cast(ce_f16x8, *reinterpret_cast<const uint4*>(&actL[idx]));
+        }
+    };
+    auto load_edge = [&](int idx, ce_f16x8& h, ce_f16x8& l) {
+        h = __builtin_bit_cast(ce_f16x8, *reinterpret_cast<const uint4*>(&actH[idx]));
+        l = __builtin_bit_cast(ce_f16x8, *reinterpret_cast<const uint4*>(&actL[idx]));
+    };
+    // term-major over the wave's groups: consecutive MFMAs write different accumulators
+    auto mma = [&](const ARegs& a, const uint4 (&bv)[2]) {
+        const ce_f16x8 bh = __builtin_bit_cast(ce_f16x8, bv[0]), bl = __builtin_bit_cast(ce_f16x8, bv[1]);
+#pragma unroll
+        for (int g = 0; g < GX; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.l[g], bh, acc[g], 0, 0, 0);
+#pragma unroll
+        for (int g = 0; g < GX; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.h[g], bl, acc[g], 0, 0, 0);
+#pragma unroll
+        for (int g = 0; g < GX; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.h[g], bh, acc[g], 0, 0, 0);
+    };
+    auto mma_edge = [&](f32x4& c, const ce_f16x8& h, const ce_f16x8& l, const uint4 (&bv)[2]) {
+        const ce_f16x8 bh = __builtin_bit_cast(ce_f16x8, bv[0]), bl = __builtin_bit_cast(ce_f16x8, bv[1]);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(l, bh, c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(h, bl, c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(h, bh, c, 0, 0, 0);
+    };
+    // One window row: `x` holds the A fragments of its first step on entry; the fragments of step s + 1 are read from LDS while the MFMAs of
+    // step s run (two register sets), the last step reads the first fragments of row rn into `y`.  The border steps' fragments are requested
+    // at the head of the row and multiplied at its end.
+    auto row = [&](int r, int rn, const BRow& o, ARegs& x, ARegs& y) {
+        ce_f16x8 eh[2], el[2];
+        if (hasL) load_edge(aL >= 0 ? aL + r * PW : ZERO, eh[0], el[0]);
+        if (hasR) load_edge(aR >= 0 ? aR + r * PW : ZERO, eh[1], el[1]);
+        load_a(r, 1, y);     mma(x, o.v[0]);
+        load_a(r, 2, x);     mma(y, o.v[1]);
+        load_a(rn, 0, y);    mma(x, o.v[2]);
+        if (hasL) mma_edge(accL, eh[0], el[0], o.v[3]);
+        if (hasR) mma_edge(accR, eh[1], el[1], o.v[4]);
+    };
+    {
+        BRow ba, bb;
+        ARegs ax, ay;
+        load_row(0, ba);
+        load_a(0, 0, ax);
+#pragma unroll 1
+        for (int r = 0; r < 20; r += 2) {
+            load_row(r + 1, bb);
+            row(r, r + 1, ba, ax, ay);
+            load_row(r + 2, ba);                                           // (r + 2 == 20: the zero row -- no branch around the loads)
+            row(r + 1, r + 2 < 20 ? r + 2 : 19, bb, ay, ax);               // (after the last row a harmless re-read)
+        }
+    }
+    CE_TPHASE(2);
+
+    // ---- epilogue: lane (lq = 2 co + dy, lg) holds pixels 4 lg .. 4 lg + 3 of output row dy, channel co of every group.  Undo the scaling, add
+    // the bias of the pixel's border variant and the addend; statistics about a per-channel shift (common.hip.h mi_stat_acc)
+    const float us = ldexpf(1.0f, -(ex + p.w_exp));
+    float bv[3];
+#pragma unroll
+    for (int vx = 0; vx < 3; ++vx) bv[vx] = bias9 ? mi_ldg(bias9 + (vy * 3 + vx) * 8 + co) : 0.0f;
+    const int wy = Ho - (oy0 + 2 * wave), wx = Wo - ox0;
+    const int wcnt = (wy <= 0 ? 0 : 2) * (wx > TWO ? TWO : wx);            // Ho is even: a row pair is inside or outside as a whole
+    float s = 0.0f, q2 = 0.0f, sh = 0.0f;
+#pragma unroll
+    for (int g = 0; g < GX; ++g) {
+        const int ox = ox0 + 16 * g + 4 * lg;
+        float y[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float a = acc[g][j];
+            if (g == 0) a += hasL ? accL[j] : 0.0f;                        // (zero except for output column 0)
+            a += (hasR && g == gR) ? accR[j] : 0.0f;                       // (zero except for output column Wo - 1)
+            const int X = ox + j;
+            y[j] = fmaf(a, us, X == 0 ? bv[0] : (X == Wo - 1 ? bv[2] : bv[1]));
+        }
+        if (p.addend) { y[0] += addv[g].x; y[1] += addv[g].y; y[2] += addv[g].z; y[3] += addv[g].w; }
+        if (g == 0 && p.out_stats) sh = __shfl(y[0], 2 * co);              // the channel's first value of the wave (lane dy = 0, lg = 0)
+        const size_t o = ((size_t)(b * 8 + co) * Ho + (oy < Ho ? oy : 0)) * Wo;
+        if (vec4) {
+            if (oy < Ho && ox < Wo) mi_stg4(p.out + o + ox, make_float4(y[0], y[1], y[2], y[3]));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (oy < Ho && ox + j < Wo) mi_stg(p.out + o + ox + j, y[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float d = (oy < Ho && ox + j < Wo) ? y[j] - sh : 0.0f;
+            s += d;
+            q2 = fmaf(d, d, q2);
+        }
+    }
+    if (p.out_stats) {
+        s += __shfl_xor(s, 1); q2 += __shfl_xor(q2, 1);
+        s += __shfl_xor(s, 16); q2 += __shfl_xor(q2, 16);
+        s += __shfl_xor(s, 32); q2 += __shfl_xor(q2, 32);
+        if (dy == 0 && lg == 0) {
+            mi_stat_acc a; a.c = sh; a.s = s; a.q = q2; a.n = wcnt;
+            mi_stat_finish(a, red[wave][2 * co], red[wave][2 * co + 1]);
+        }
+        __syncthreads();
+        if (tid < 16) p.out_stats[((size_t)(b * 8 + (tid >> 1)) * gridDim.x + tile) * 2 + (tid & 1)] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+    }
+    CE_TPHASE(3);
+    CE_TEND();
+}
+
 // ---- generic (any dim / kernel sizes): one work-item per output pixel, CPT output channels of one member per blockIdx.z; taps read
 // through L1/L2.  Correct for every constructor argument.  CPT = 8 where every member's channel count is a multiple of 8 (the wide presets:
 // dim 128 -> 64 + 32 + 32): the tap's load and bounds logic serve eight FMAs, the weights of a tap are one wave-uniform 32-byte load -- Unet()'s
@@ -581,4 +827,29 @@ extern "C" int mi_crossembed_fwd(const mi_crossembed_params* pp, void* stream) {
         }
     }
     return mi_check_launch("crossembed");
+}
+
+extern "C" int mi_init_down_tiles(int tile_cfg, int H, int W) {
+    if ((tile_cfg != 0 && tile_cfg != 1) || H < 4 || W < 4 || (H & 1) || (W & 3)) return -1;
+    const int two = tile_cfg == 0 ? 64 : 32;
+    return ((H / 2 + 7) / 8) * ((W / 2 + two - 1) / two);
+}
+
+extern "C" int mi_init_down_fwd(const mi_init_down_params* pp, void* stream) {
+    const mi_init_down_params& p = *pp;
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = mi_init_down_tiles(p.tile_cfg, p.H, p.W);
+    if (p.B <= 0 || tiles < 0) { mi_set_error("mi_init_down_fwd: B > 0, H and W >= 4, H even, W %% 4 == 0, tile_cfg 0 / 1"); return MI_ERR_INVALID; }
+    if (!p.in0 || !p.w_tab || !p.out) { mi_set_error("mi_init_down_fwd: in0, w_tab and out must be set"); return MI_ERR_INVALID; }
+    int ctot = 0;
+    bool ks_ok = p.n_kernels >= 1 && p.n_kernels <= 3;
+    for (int i = 0; ks_ok && i < p.n_kernels; ++i) { ks_ok = (p.ksize[i] & 1) && p.ksize[i] >= 1 && p.ksize[i] <= 15 && p.cout[i] > 0; ctot += p.cout[i]; }
+    if (!ks_ok || ctot > 16 || p.Cout != 8 || p.C0 < 1 || p.C0 > 4 || p.in1 || p.C1 || p.out_st) {
+        mi_set_error("mi_init_down_fwd: built for a CrossEmbed of <= 3 odd kernels <= 15 with <= 16 channels, 8 Downsample channels, one input of <= 4 channels, fp32 storage");
+        return MI_ERR_UNSUPPORTED;
+    }
+    const uint4* wt = (const uint4*)p.w_tab;
+    if (p.tile_cfg == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(init_down_mfma_kernel<4>), dim3(tiles, p.B), dim3(256), 0, st, p, wt, p.bias9);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(init_down_mfma_kernel<2>), dim3(tiles, p.B), dim3(256), 0, st, p, wt, p.bias9);
+    return mi_check_launch("init_down_mfma");
 }

@@ -32,6 +32,7 @@ CONV_WIDE_GEMM = os.environ.get("MINIMAGEN_CONV_WIDE_GEMM", "1") != "0"   # wide
 COND_GEMM = int(os.environ.get("MINIMAGEN_COND_GEMM", "2048"))           # stacked time-MLPs with at least this many rows run as one GEMM per step (0 = always inside cond_step_kernel)
 FLASH_KV_PREP = os.environ.get("MINIMAGEN_FLASH_KV_PREP", "1") != "0"     # multi-query self-attention of the wide presets: K / V prepared once per launch, LDS-DMA into the workgroups
 CE_MFMA = os.environ.get("MINIMAGEN_CE_MFMA", "1") != "0"                  # CrossEmbed on the matrix cores (0: the fp32 VALU kernel)
+INIT_DOWN = os.environ.get("MINIMAGEN_INIT_DOWN", "1") != "0"              # CrossEmbed + the first level's pre-Downsample as one launch (0: the two launches)
 CONV_REVERSE = int(os.environ.get("MINIMAGEN_CONV_REVERSE", "1"))        # a row-paired conv walks the image groups opposite to its producer (0 = off)
 RP_NTILE = int(os.environ.get("MINIMAGEN_RP_NTILE", "0"))               # tiles per workgroup of the row-paired kernel (0 = the library's choice)
 RP_NTILE_BY = {k: int(os.environ.get("MINIMAGEN_RP_NTILE_" + k, "0")) for k in ("L", "M", "S")}     # ... per image-size class (> 128^2 / > 64^2 / smaller)
@@ -315,8 +316,29 @@ class UnetEngine:
         if CE_MFMA and [c.kernel_size[0] for c in cvs] == [3, 7, 15] and [c.out_channels for c in cvs] == [4, 2, 2] and u.channels <= 4:
             for chan0 in range(0, cvs[0].in_channels, u.channels):
                 pk.ce_mfma[chan0] = P.pack_crossembed_mfma([c.weight for c in cvs], chan0, u.channels)
+        # CrossEmbed o pre-Downsample of a memory_efficient U-Net as one composed convolution (csrc/crossembed.hip init_down_mfma_kernel): both
+        # are linear, and nothing else reads the full-resolution tensor between them.  The tables are composed by the first fp32 workspace
+        # that uses them (_init_down_tables); MINIMAGEN_CE_MFMA=0 (the fp32 VALU CrossEmbed) keeps the two launches as well
+        pk.init_down = {}
+        pre0 = u.downs[0][0]
+        pk.init_down_ok = INIT_DOWN and CE_MFMA and isinstance(pre0, nn.Conv2d) and pre0.kernel_size == (4, 4) and pre0.stride == (2, 2) \
+            and pre0.padding == (1, 1) and pre0.out_channels == 8 and len(cvs) <= 3 and all(c.kernel_size[0] % 2 == 1 and c.kernel_size[0] <= 15 for c in cvs) \
+            and sum(c.out_channels for c in cvs) <= 16 and u.channels <= 4 and not u.init_conv_to_final_conv_residual
         self._pack, self._pack_key = pk, key
         return pk
+
+    def _init_down_tables(self, pk):
+        """the composed CrossEmbed o Downsample tables of both input halves (packing.compose_init_down, fp64 on the host), once per pack"""
+        if not pk.init_down:
+            u = self.unet
+            cvs, pre0 = u.init_conv.convs, u.downs[0][0]
+            dev = pre0.weight.device
+            for chan0 in range(0, cvs[0].in_channels, u.channels):
+                x_half = chan0 == 0                 # the biases of both layers ride on the x half
+                w9, b9 = P.compose_init_down([c.weight for c in cvs], [c.bias for c in cvs] if x_half else None, pre0.weight, pre0.bias, chan0, u.channels)
+                tab, exp, b32 = P.pack_init_down_mfma(w9, b9)
+                pk.init_down[chan0] = (tab.to(dev), exp, b32.to(dev) if x_half else None)
+        return pk.init_down
 
     # ------------------------------------------------------------------ workspace / program
     def packed(self):
@@ -793,9 +815,10 @@ class UnetEngine:
             lib.mi_conv_tile_shape(cfg, C.byref(th), C.byref(tw))
             nt = -(-H // th.value) * -(-W // tw.value)
         ctot = sum(u.init_conv.dim_scales)
-        cur = self._new_act(ws, B, ctot, H, W, nt)
         if len(u.init_conv.convs) > 3:
             raise NotImplementedError("CrossEmbedLayer with more than 3 kernel sizes")
+        # fp32 only: the reduced-precision configuration keeps the two launches
+        init_down = pk.init_down_ok and not ws.half and not ws.store16 and H >= 4 and W >= 4 and H % 2 == 0 and W % 4 == 0
 
         def ce_params(src, chan0, with_bias, out_t, out_stats, addend):
             ce = L.MiCrossEmbedParams()
@@ -816,17 +839,42 @@ class UnetEngine:
                     ce.w_mfma_exp[i] = exps[i]
             return ce
 
+        def id_params(src, chan0, out_t, out_stats, addend, id_cfg):
+            q = L.MiInitDownParams()
+            q.B, q.H, q.W = B, H, W
+            q.in0, q.C0 = L.ptr(src), u.channels
+            q.n_kernels = len(u.init_conv.convs)
+            for i, cv in enumerate(u.init_conv.convs):
+                q.ksize[i], q.cout[i] = cv.kernel_size[0], cv.out_channels
+            tab, q.w_exp, b9 = pk.init_down[chan0]
+            q.Cout, q.w_tab, q.bias9 = 8, L.ptr(tab), L.ptr(b9)
+            q.out, q.out_stats, q.tile_cfg, q.addend = L.ptr(out_t), L.ptr(out_stats), id_cfg, L.ptr(addend)
+            return q
+
         ws.prog_pre = []
-        if u.lowres_cond:
-            ws.ce_lr = torch.zeros(B, ctot, H, W, dtype=torch.bfloat16 if ws.store16 else torch.float32, device=ws.dev)
-            ws.prog_pre.append((lib.mi_crossembed_fwd, ce_params(ws.lowres, u.channels, False, ws.ce_lr, None, None), "crossembed_lowres"))
-            ws.prog.append((lib.mi_crossembed_fwd, ce_params(ws.x, 0, True, cur.t, cur.stats, ws.ce_lr), "crossembed"))
+        if init_down:
+            self._init_down_tables(pk)
+            # one launch from the image to the first level's half-resolution tensor; the hoisted low-res half is half resolution too.  The plan
+            # entries keep CrossEmbed's names.  Tile shape by image size only (the statistics tiles must not depend on the batch)
+            id_cfg = 0 if W // 2 >= 64 else 1
+            cur = self._new_act(ws, B, 8, H // 2, W // 2, lib.mi_init_down_tiles(id_cfg, H, W))
+            fn = lib.mi_init_down_fwd
+            if u.lowres_cond:
+                ws.ce_lr = torch.zeros(B, 8, H // 2, W // 2, dtype=torch.float32, device=ws.dev)
+                ws.prog_pre.append((fn, id_params(ws.lowres, u.channels, ws.ce_lr, None, None, id_cfg), "crossembed_lowres"))
+            ws.prog.append((fn, id_params(ws.x, 0, cur.t, cur.stats, ws.ce_lr if u.lowres_cond else None, id_cfg), "crossembed"))
         else:
-            ws.prog.append((lib.mi_crossembed_fwd, ce_params(ws.x, 0, True, cur.t, cur.stats, None), "crossembed"))
+            cur = self._new_act(ws, B, ctot, H, W, nt)
+            if u.lowres_cond:
+                ws.ce_lr = torch.zeros(B, ctot, H, W, dtype=torch.bfloat16 if ws.store16 else torch.float32, device=ws.dev)
+                ws.prog_pre.append((lib.mi_crossembed_fwd, ce_params(ws.lowres, u.channels, False, ws.ce_lr, None, None), "crossembed_lowres"))
+                ws.prog.append((lib.mi_crossembed_fwd, ce_params(ws.x, 0, True, cur.t, cur.stats, ws.ce_lr), "crossembed"))
+            else:
+                ws.prog.append((lib.mi_crossembed_fwd, ce_params(ws.x, 0, True, cur.t, cur.stats, None), "crossembed"))
 
         hiddens: List[Act] = []
-        for pre, init_block, resnet_blocks, attn_block, post in u.downs:
-            if isinstance(pre, nn.Conv2d):
+        for level, (pre, init_block, resnet_blocks, attn_block, post) in enumerate(u.downs):
+            if isinstance(pre, nn.Conv2d) and not (init_down and level == 0):
                 cur = self._emit_conv(ws, pk, cur, None, wpack=pk.conv[id(pre)], bias=pre.bias, Cout=pre.out_channels, ksize=4, stride=2)
             cur = self._emit_resnet(ws, pk, init_block, cur, None)
             for rb in resnet_blocks:

@@ -247,3 +247,79 @@ def pack_crossembed_mfma_device(ws, idx: torch.Tensor, exps):
     hi = t.half()
     lo = (t - hi.float()).half()
     return torch.stack((hi, lo), dim=2).reshape(CE_TABLE_ROWS, 256).contiguous()
+
+
+# ---- CrossEmbed o Downsample(k4 s2) as ONE convolution (csrc/crossembed.hip init_down_mfma_kernel) ----
+ID_TAPS = 18              # 15 + 4 - 1: the composed kernel is 18 x 18, stride 2, pad 8
+ID_ROWS = 3 * ID_TAPS + 1   # table rows: [vertical variant][vertical tap] + one all-zero row
+ID_STEPS = 5              # K = 32 steps of a table row: horizontal taps 0-7, 8-15, 16-23 | left-border correction | right-border correction
+
+
+def compose_init_down(ce_ws, ce_bs, wd, bd, chan0: int, cin: int):
+    """CrossEmbedLayer (odd kernel sizes <= 15, layers.py:254-305) followed by Downsample = Conv2d(k4, s2, p1) (Unet.py:415-416; nothing
+    but the zero padding in between) as one 18 x 18 stride-2 pad-8 convolution, in fp64.
+
+    ce_ws: the CrossEmbed weights [cout_i][Cin_total][k_i][k_i], ce_bs: their biases (or None: the low-res half carries no bias at all, then
+    bd is ignored too), wd [Co][sum cout_i][4][4], bd [Co]; input channels chan0 .. chan0 + cin - 1 are composed.
+    The reference zero-pads the INTERMEDIATE by one pixel, so the Downsample taps that land on intermediate row -1 / H (column -1 / W) are
+    left out of the weights and of the bias: variant 0 (first output row / column) drops tap 0, variant 2 (last) drops tap 3, variant 1
+    (interior) keeps all four.  Returns (W9 [3 vy][3 vx][Co][cin][18][18], b9 [3][3][Co]) float64: with the variant chosen by the output
+    pixel's position the composition is exact."""
+    ks = [w.shape[-1] for w in ce_ws]
+    assert all(k % 2 == 1 and k <= 15 for k in ks) and tuple(wd.shape[2:]) == (4, 4)
+    m_tot = sum(w.shape[0] for w in ce_ws)
+    assert wd.shape[1] == m_tot
+    wc = torch.zeros(m_tot, cin, 15, 15, dtype=torch.float64)
+    m0 = 0
+    for w, k in zip(ce_ws, ks):
+        o = (15 - k) // 2
+        wc[m0:m0 + w.shape[0], :, o:o + k, o:o + k] = w.detach().double().cpu()[:, chan0:chan0 + cin]
+        m0 += w.shape[0]
+    wdd = wd.detach().double().cpu()
+    co = wdd.shape[0]
+    with_bias = ce_bs is not None
+    bc = torch.cat([b.detach().double().cpu() for b in ce_bs]) if with_bias else torch.zeros(m_tot, dtype=torch.float64)
+    taps = ((1, 2, 3), (0, 1, 2, 3), (0, 1, 2))
+    w9 = torch.zeros(3, 3, co, cin, ID_TAPS, ID_TAPS, dtype=torch.float64)
+    b9 = torch.zeros(3, 3, co, dtype=torch.float64)
+    for vy in range(3):
+        for vx in range(3):
+            for a in taps[vy]:
+                for b in taps[vx]:
+                    w9[vy, vx, :, :, a:a + 15, b:b + 15] += torch.einsum('om,mcyx->ocyx', wdd[:, :, a, b], wc)
+                    b9[vy, vx] += wdd[:, :, a, b] @ bc
+            if with_bias and bd is not None:
+                b9[vy, vx] += bd.detach().double().cpu()
+    return w9, b9
+
+
+def pack_init_down_mfma(w9: torch.Tensor, b9: torch.Tensor):
+    """compose_init_down's variants as the B-operand table of init_down_mfma_kernel (8 output channels, <= 4 input channels).
+
+    The GEMM is Toeplitz in the vertical direction: N = (output channel co, output row dy of a row pair), a lane supplies two adjacent
+    columns x 4 channels (8 fp16) of one window row, the 4 lane groups lg make up K = 32.  A B operand depends on (window row - 2 dy, vertical
+    variant of the lane's output row) only, so the table holds one row per (vy, vertical tap ty) -- row 18 vy + ty, row 54 all zero -- and every
+    lane reads its own row.  A row holds five K = 32 steps [step][hi | lo][co 8][lg 4][8 fp16 = 4 dx + ci]:
+      steps 0-2: the interior-column variant, horizontal taps tx = 8 step + 2 lg + dx (tx >= 18: zero);
+      step 3:    (left-column variant - interior) at tx = 8 + 2 lg + dx: multiplies image columns 0 .. 7 for the output pixel of column 0 only;
+      step 4:    (right-column variant - interior) at tx = 2 + 2 lg + dx: image columns W - 8 .. W - 1 for the last output column only.
+    (The difference of two variants vanishes outside those taps once the zero padding of the image is taken into account.)
+    Pre-scaled by one power of two so that max|w| lands in [128, 256), split into fp16 hi | lo.  Returns (table [55][5 * 2 * 8 * 4 * 8] fp16,
+    exponent, bias [3][3][8] fp32)."""
+    co, cin = w9.shape[2], w9.shape[3]
+    assert co == 8 and cin <= 4 and tuple(w9.shape[4:]) == (ID_TAPS, ID_TAPS)
+    wp = torch.zeros(3, 3, co, 4, ID_TAPS, 24, dtype=torch.float64)
+    wp[:, :, :, :cin, :, :ID_TAPS] = w9
+    exp = rp_weight_exponent(float(wp.abs().max()))
+    wp = wp * (2.0 ** exp)
+    tab = torch.zeros(ID_ROWS, ID_STEPS, co, 4, 2, 4, dtype=torch.float64)       # [row][step][co][lg][dx][ci]
+    f = lambda t, n: t.reshape(3, co, 4, ID_TAPS, n, 4, 2).permute(0, 3, 4, 1, 5, 6, 2)     # [vy][co][ci][ty][n lg dx] -> [vy][ty][n][co][lg][dx][ci]
+    main = tab[:3 * ID_TAPS].reshape(3, ID_TAPS, ID_STEPS, co, 4, 2, 4)
+    main[:, :, 0:3] = f(wp[:, 1], 3)
+    main[:, :, 3] = f((wp[:, 0] - wp[:, 1])[..., 8:16], 1)[:, :, 0]
+    main[:, :, 4] = f((wp[:, 2] - wp[:, 1])[..., 2:10], 1)[:, :, 0]
+    t = tab.reshape(ID_ROWS, ID_STEPS, co, 4, 8)
+    hi = t.float().half()
+    lo = (t - hi.double()).float().half()
+    out = torch.stack((hi, lo), dim=2)                                           # [row][step][hl][co][lg][8]
+    return out.reshape(ID_ROWS, -1).contiguous(), exp, b9.float().contiguous()
