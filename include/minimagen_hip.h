@@ -230,7 +230,10 @@ int mi_cond_step_fwd(const mi_cond_step_params* p, void* stream);
  *     out   = sum_h softmax(sim_h) . (c . Wv_h^T Wo_h^T)
  * so the 512-wide q/k/v/out tensors never exist.  mi_attn_fold_rows turns context rows into
  * MFMA A-operand fragments ("gv"); mi_cross_attn_fwd does LN -> QK^T -> softmax -> PV ->
- * to_out.1 LayerNorm -> + residual with v_mfma_f32_16x16x4_f32 (exact fp32).
+ * to_out.1 LayerNorm -> + residual on the matrix cores (variant 6: 3-term fp16 split, fp32-grade; 7: single term).
+ * Where cond_dim <= 8 < C both bilinear forms have rank cond_dim and variant 8 contracts over cond_dim instead: context operands
+ * without a head axis (mi_attn_cond_rows), 41 instead of 61 matrix instructions per head and wave -- described after
+ * mi_cross_attn_params.
  *   gv layout: [B2][heads][JT][64 lanes][FR], FR = max(4, C/4) + 4*ceil(C/16); context row j
  *   lives in tile j/16.  Row 0 is the null key/value, rows 1.. the time tokens, then 256 text rows. */
 #define MI_ATTN_MAX_BLOCKS 8
@@ -281,9 +284,40 @@ typedef struct mi_cross_attn_params {
                                        2^v_exp (mi_attn_fold_params); the kernel undoes all three exactly (scores, output) */
     int variant;                    /* 6: 16 tokens per wave with the contractions as 3-term fp16 splits on v_mfma_f32_16x16x32_f16
                                        (hi*hi + hi*lo + lo*hi, ~2^-21: fp32-grade); 7: as 6 with a single fp16 term (reduced-precision
-                                       configuration, same frag_f16 fragments).  (0 .. 5, the exact-fp32 MFMA yardsticks of rounds 1-5, are gone: ABI 10) */
+                                       configuration, same frag_f16 fragments).  (0 .. 5, the exact-fp32 MFMA yardsticks of rounds 1-5, are gone: ABI 10)
+                                       8: as 6 with both contractions run over cond_dim (see below); C in {8, 16}, cd <= 8, 8 heads, 17 context tiles */
+    const float* head_tab;          /* variant 8: per-head tables [heads][mi_attn_cond_head_floats()] (packing.pack_cross_attn_cond); gv then points
+                                       at mi_attn_cond_rows fragments, g_exp is the scores' f_exp + c_exp and v_exp the output's c_exp + mv_exp */
 } mi_cross_attn_params;
 int mi_cross_attn_fwd(const mi_cross_attn_params* p, void* stream);
+
+/* Variant 8: the fold contracted on the other side.  In the BASELINE U-Nets cond_dim = 8 < C, so both bilinear forms have rank 8 and the
+ * per-head expansion of every context row to C values (variant 6's gv: 37 KB per batch row AND head) is work the result does not need:
+ *     s_hj  = y~_h . c~_j,   y~_h = (MG_h^T x^, g0_h . x^) in R^9,   c~_j = (c_j, 0) for j >= 1,  c~_0 = (0, 1) (the null key)
+ *     out_h = MV_h (sum_{j>=1} p_hj c_j) / l_h + (p_h0 / l_h) v0_h
+ * The context operands hold context only -- one set per batch row, shared by all heads and all cross-attention blocks of a U-Net:
+ *   frag [B2][JT + ceil(JT/2)][64 lanes][8 halves]:
+ *     rows 0 .. JT-1 (scores, tile t, lane (j = lane & 15, lg = lane >> 4)): e = 0..2: c hi[3lg + e], e = 3..5: the same again (they meet
+ *       y lo), e = 6, 7: c lo[2lg + e - 6]; dimension 8 is the null indicator 2^i_exp of row 0, dimensions 9..11 are zero
+ *     rows JT .. (P.V, tile pair q, lane (m = lane & 15, lg)): e = 0..3: row m at j = 32q + 4lg + e, e = 4..7: at j = 32q + 16 + 4lg + e - 4;
+ *       row m < 8 is c hi[m], row m >= 8 is c lo[m - 8]; context row 0 stays zero (the null value is added in fp32)
+ *   All values are c * 2^c_exp.  The buffer is allocated zero-filled: rows past J must read as finite zeros.
+ * With t_state the rows come from a table [steps][nrows][cd] shared by every batch row (the time tokens depend on the timestep only) and
+ * the launch also copies that step's scale/shift rows, exactly like modes 2 / 3 of mi_attn_fold_rows. */
+typedef struct mi_attn_cond_params {
+    int B2, cd, JT;
+    const float* c_rows;            /* [B2][nrows][cd] rows (already norm_cond-ed), or the table [steps][nrows][cd] with t_state */
+    int c_stride_b;                 /* floats between consecutive b' (or steps) in c_rows */
+    int row0, nrows;                /* they become context rows row0 .. row0+nrows-1 */
+    int write_null;                 /* also write context row 0: the indicator */
+    int c_exp, i_exp;
+    float* frag;
+    const int* t_state; int t_off;  /* the step is *t_state - t_off */
+    const float* ss_all; float* ss; int ss_n;
+} mi_attn_cond_params;
+int mi_attn_cond_rows(const mi_attn_cond_params* p, void* stream);
+int mi_attn_cond_frag_floats(int JT);   /* per batch row */
+int mi_attn_cond_head_floats(void);     /* per head */
 #define MI_ATTN_TOKENS_PER_WG 128
 
 /* ---- sampler (Imagen._p_mean_variance / _p_sample, Imagen.py:261-370) ------------------

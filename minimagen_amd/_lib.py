@@ -103,6 +103,15 @@ class MiCrossAttnParams(C.Structure):
         ("B2", C.c_int), ("C", C.c_int), ("HW", C.c_int), ("heads", C.c_int), ("J", C.c_int),
         ("x", MiAct), ("gv", C.c_void_p), ("n1_g", C.c_void_p), ("n1_b", C.c_void_p), ("n2_g", C.c_void_p), ("n2_b", C.c_void_p),
         ("out", C.c_void_p), ("out_stats", C.c_void_p), ("out_st", C.c_int), ("x_exp", C.c_int), ("g_exp", C.c_int), ("v_exp", C.c_int), ("variant", C.c_int),
+        ("head_tab", C.c_void_p),
+    ]
+
+
+class MiAttnCondParams(C.Structure):
+    _fields_ = [
+        ("B2", C.c_int), ("cd", C.c_int), ("JT", C.c_int), ("c_rows", C.c_void_p), ("c_stride_b", C.c_int), ("row0", C.c_int), ("nrows", C.c_int),
+        ("write_null", C.c_int), ("c_exp", C.c_int), ("i_exp", C.c_int), ("frag", C.c_void_p),
+        ("t_state", C.c_void_p), ("t_off", C.c_int), ("ss_all", C.c_void_p), ("ss", C.c_void_p), ("ss_n", C.c_int),
     ]
 
 
@@ -211,7 +220,7 @@ class MiPackConv3Desc(C.Structure):
 _STRUCTS = {0: MiAct, 1: MiConvParams, 2: MiCrossEmbedParams, 3: MiLinear, 4: MiTextCondParams, 5: MiCondStepParams,
             6: MiAttnFoldParams, 7: MiCrossAttnParams, 8: MiCfgX0Params, 9: MiQuantileParams, 10: MiPosteriorParams,
             11: MiResizeParams, 12: MiSelfAttnParams, 13: MiChanFFParams, 14: MiFlashAttnParams, 15: MiTokensToNchwParams, 16: MiConvWgradParams, 17: MiBlockBwdParams, 18: MiCrossEmbedWgradParams, 19: MiFoldedAttnParams, 20: MiAdamTensor, 21: MiAdamParams, 22: MiPackConv3Desc,
-            23: MiFlashAttnTrainParams, 24: MiSamplerExtParams, 25: MiInpaintParams, 26: MiInitDownParams}
+            23: MiFlashAttnTrainParams, 24: MiSamplerExtParams, 25: MiInpaintParams, 26: MiInitDownParams, 27: MiAttnCondParams}
 
 _lib = None
 _backend = None
@@ -230,7 +239,7 @@ def _bind(lib):
     for name in ("mi_conv_fwd", "mi_gn_coef_fwd", "mi_crossembed_fwd", "mi_text_cond_fwd", "mi_cond_step_fwd", "mi_attn_fold_rows", "mi_cross_attn_fwd",
                  "mi_cfg_x0_fwd", "mi_quantile_fwd", "mi_posterior_fwd", "mi_resize_fwd", "mi_self_attn_fwd", "mi_chan_ff_fwd",
                  "mi_flash_attn_fwd", "mi_conv_prep_fwd", "mi_tokens_to_nchw_fwd", "mi_conv_wgrad", "mi_block_bwd", "mi_crossembed_wgrad", "mi_folded_attn_fwd", "mi_folded_attn_bwd", "mi_adam_step",
-                 "mi_flash_attn_train_fwd", "mi_flash_attn_train_bwd", "mi_init_down_fwd"):
+                 "mi_flash_attn_train_fwd", "mi_flash_attn_train_bwd", "mi_init_down_fwd", "mi_attn_cond_rows"):
         getattr(lib, name).argtypes = [vp, vp]
         getattr(lib, name).restype = i32
     lib.mi_conv_prep_bytes.argtypes = [i32, i32, i32, i32, i32]
@@ -295,6 +304,8 @@ def _bind(lib):
     lib.mi_pack_conv3.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp]
     lib.mi_pack_conv3_multi.argtypes = [vp, i32, i32, vp]
     lib.mi_attn_fragment_floats.argtypes = [i32]
+    lib.mi_attn_cond_frag_floats.argtypes = [i32]
+    lib.mi_attn_cond_head_floats.argtypes = []
     for which, st in _STRUCTS.items():
         n = lib.mi_struct_size(which)
         if n != C.sizeof(st):

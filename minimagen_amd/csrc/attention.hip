@@ -295,7 +295,233 @@ __global__ __launch_bounds__(64 * NWV, WPS) void cross_attn_f16x3_kernel(const m
     }
 }
 
+// ---- variant 8: the 3-term kernel with both contractions run over cond_dim (<= 8) instead of over the C image channels.
+// Scores: s_hj = y~_h . c~_j with y~_h = (MG_h^T x^, g0_h . x^) (9 values per token and head) and c~_j = (c_j, 0), c~_0 = (0, 1): the A operand of
+// the score instruction holds context only and is shared by all heads, ONE K = 32 instruction per context tile.  Its 32 K slots, lane
+// group lg, element e:  e = 0..2: c hi[d = 3 lg + e] . y hi[d]   e = 3..5: c hi[d = 3 lg + e - 3] . y lo[d]   e = 6, 7: c lo[d = 2 lg + e - 6] . y hi[d]
+// (d = 8: the null key's indicator, d > 8: zero).  y~_h itself is two 16-row products F_h . x^ (2 instructions each, the 3-term form of variant 6)
+// whose rows are ordered like those slots: accumulator r of product T IS slot e = 4 T + r of the same lane, so y~ never crosses lanes.
+// P.V: u = sum_j p_j c_j with the A operand {c hi (8 rows) ; c lo (8 rows)} per PAIR of context tiles, B = P hi then P lo (2 instructions per
+// pair); then out += [MV_h | MV_h] . split(u / l) (2 instructions per head, chained into ONE accumulator over the heads: the duplicated columns
+// add the c hi and c lo halves) and the null value as 4 fp32 FMAs.  Per head and wave 4 + 17 + 18 + 2 = 41 instructions (variant 6: 61).
+// Everything a workgroup reads from LDS is loaded once: the context fragments of its batch row (mi_attn_cond_rows) and the per-head
+// tables (packing.pack_cross_attn_cond, weights only); no per-head streaming, no per-head barrier.
+// The softmax (max, packed exponent arguments, exp2, packed sum, split of P) is variant 6's, instruction for instruction.
+#define MI_COND_HEAD_ROWS 5         // per head: F tiles 0 / 1, {MV hi | MV hi}, {MV lo | 0}, v0 (fp32)
+template <int C, int NWV>
+__global__ __launch_bounds__(64 * NWV, 4) void cross_attn_cond_f16x3_kernel(const mi_cross_attn_params p) {
+    static_assert(C <= 16, "one channel chunk");
+    constexpr int JT = 17, JP = (JT + 1) / 2, CROWS = JT + JP, HEADS = 8, HROWS = MI_COND_HEAD_ROWS * HEADS, TOK_WG = 16 * NWV;
+    __shared__ double red[NWV][2 * 16];
+    __shared__ __attribute__((aligned(16))) uint4 ctx[CROWS * 64];       // [tile] score operands, then [tile pair] P.V operands
+    __shared__ __attribute__((aligned(16))) uint4 htab[HROWS * 64];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lq = lane & 15, lg = lane >> 4;
+    const int tiles = (p.HW + TOK_WG - 1) / TOK_WG;
+    int b, tile;
+    if ((p.B2 & 7) == 0) {
+        const int L = blockIdx.x, k = L >> 3;
+        b = (L & 7) + 8 * (k / tiles);
+        tile = k % tiles;
+    } else {
+        b = blockIdx.x / tiles;
+        tile = blockIdx.x % tiles;
+    }
+    // the whole LDS image, once: LDS-DMA (no registers, asynchronous) under the LayerNorm below
+    {
+        const uint4* csrc = reinterpret_cast<const uint4*>(p.gv) + (size_t)b * CROWS * 64;
+        const uint4* hsrc = reinterpret_cast<const uint4*>(p.head_tab);
+        for (int r = wave; r < CROWS + HROWS; r += NWV) {               // one 1 KB row (64 lanes x 16 bytes) per instruction
+            const uint4* src = (r < CROWS ? csrc + (size_t)r * 64 : hsrc + (size_t)(r - CROWS) * 64) + lane;
+            uint4* dst = r < CROWS ? &ctx[r * 64] : &htab[(r - CROWS) * 64];
+#if defined(HIPEMU)
+            dst[lane] = *src;
+#else
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+#endif
+        }
+    }
+    const int bx = mi_row_of(b, p.x.bmod);
+    const int i = (tile * NWV + wave) * 16 + lq;
+    const bool ok = i < p.HW;
+    const float* xb = p.x.data + (size_t)bx * C * p.HW;
+    auto ldx = [&](int a) -> float { return xb[(size_t)a * p.HW + i]; };
+
+    // LayerNorm(x) -> B operand of the y~ products: this lane supplies channels a = 4lg + e of token lq
+    f16x4 xhi, xlo;
+    {
+        float xf[4];
+        float s = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int a = 4 * lg + e;
+            xf[e] = (ok && a < C) ? ldx(a) * p.x.scale : 0.0f;
+            s += xf[e];
+        }
+        s += __shfl_xor(s, 16); s += __shfl_xor(s, 32);
+        const float mean = s / (float)C;
+        float v = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const float d = (4 * lg + e < C) ? xf[e] - mean : 0.0f; v = fmaf(d, d, v); }
+        v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+        const float rstd = 1.0f / sqrtf(v / (float)C + 1e-5f);
+        float xn[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int a = 4 * lg + e;
+            xn[e] = (a < C) ? ldexpf((xf[e] - mean) * rstd * p.n1_g[a] + p.n1_b[a], p.x_exp) : 0.0f;
+        }
+        split_f16(xn, xhi, xlo);
+    }
+    const f16x4 z4 = {(_Float16)0, (_Float16)0, (_Float16)0, (_Float16)0};
+    const f16x8 xhh = __builtin_shufflevector(xhi, xhi, 0, 1, 2, 3, 4, 5, 6, 7);
+    const f16x8 xl0 = __builtin_shufflevector(xlo, z4, 0, 1, 2, 3, 4, 5, 6, 7);
+    f32x4 oacc = (f32x4){0.f, 0.f, 0.f, 0.f};             // sum_h MV_h u_h / l_h, scaled by 2^v_exp: chained through every head's two instructions
+    float onull[4] = {0.f, 0.f, 0.f, 0.f};                // sum_h (p_h0 / l_h) v0_h, fp32
+    const int jlast = p.J - 1;
+#if !defined(HIPEMU)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's share of the LDS image has landed ...
+#endif
+    __syncthreads();                                    // ... and everybody's has
+
+    for (int h = 0; h < HEADS; ++h) {
+        const uint4* ht = &htab[h * MI_COND_HEAD_ROWS * 64];
+        // y~_h: rows ordered as the score instruction's K slots (see above)
+        f16x8 yb;
+        {
+            f32x4 y[2];
+#pragma unroll
+            for (int T = 0; T < 2; ++T) {
+                const f16x8 f = __builtin_bit_cast(f16x8, ht[T * 64 + lane]);          // {F hi | F lo}
+                f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(f, xl0, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(f, xhh, acc, 0, 0, 0);
+                y[T] = acc;
+            }
+            const float ys[8] = {y[0][0], y[0][1], y[0][2], y[0][3], y[1][0], y[1][1], y[1][2], y[1][3]};
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                const _Float16 hi = (_Float16)ys[e];
+                yb[e] = hi;
+                yb[e + 3] = (_Float16)(ys[e + 3] - (float)hi);         // rows e and e + 3 of the table are the same functional
+            }
+            yb[6] = (_Float16)ys[6];
+            yb[7] = (_Float16)ys[7];
+        }
+        f32x4 s[JT];
+        uint4 gq[2];                                       // the next tile's fragment is read while this tile multiplies
+        gq[0] = ctx[lane];
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt) {
+            if (jt + 1 < JT) gq[(jt + 1) & 1] = ctx[(jt + 1) * 64 + lane];
+            __builtin_amdgcn_sched_barrier(0);
+            s[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, gq[jt & 1]), yb, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        }
+        float m = -INFINITY;
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (jt == JT - 1 && (16 * jt + 4 * lg + r) > jlast) s[jt][r] = -INFINITY;
+                m = fmaxf(m, s[jt][r]);
+            }
+        m = fmaxf(m, __shfl_xor(m, 16));
+        m = fmaxf(m, __shfl_xor(m, 32));
+        const float sc = ldexpf(1.0f, -(p.x_exp + p.g_exp)), msc = -m * sc;      // undo the operand scalings inside the subtraction's FMA
+        mi_f32x2 l2 = {0.0f, 0.0f};
+        const mi_f32x2 sc2 = {sc, sc}, msc2 = {msc, msc};
+        f32x4 u = (f32x4){0.f, 0.f, 0.f, 0.f};            // rows 4lg + r: lg 0, 1: c hi . P, lg 2, 3: c lo . P
+        float p0 = 0.0f;
+        // the B operand is the C/D layout of the two score tiles as it is: P[j = 16t + 4lg + e][token lq]
+#pragma unroll
+        for (int jp = 0; jp < JP; ++jp) {
+            f16x4 ph[2], pl[2];
+#pragma unroll
+            for (int ts = 0; ts < 2; ++ts) {
+                const int jt = 2 * jp + ts;
+                float pe[4] = {0.f, 0.f, 0.f, 0.f};
+                if (jt < JT) {
+                    // exponent arguments and the running sum on packed pairs (v_pk_fma_f32 / v_pk_add_f32)
+                    const f32x4 sv = s[jt < JT ? jt : 0];
+                    const mi_f32x2 a01 = mi_pk_fma((mi_f32x2){sv[0], sv[1]}, sc2, msc2), a23 = mi_pk_fma((mi_f32x2){sv[2], sv[3]}, sc2, msc2);
+                    pe[0] = __builtin_amdgcn_exp2f(a01[0]); pe[1] = __builtin_amdgcn_exp2f(a01[1]);
+                    pe[2] = __builtin_amdgcn_exp2f(a23[0]); pe[3] = __builtin_amdgcn_exp2f(a23[1]);
+                    l2 = mi_pk_add(l2, (mi_f32x2){pe[0], pe[1]});
+                    l2 = mi_pk_add(l2, (mi_f32x2){pe[2], pe[3]});
+                    if (jt == 0) p0 = pe[0];               // the null key's weight: context row 0 lives in lane group 0
+                }
+                split_f16(pe, ph[ts], pl[ts]);
+            }
+            const f16x8 phi = __builtin_shufflevector(ph[0], ph[1], 0, 1, 2, 3, 4, 5, 6, 7);
+            const f16x8 plo = __builtin_shufflevector(pl[0], pl[1], 0, 1, 2, 3, 4, 5, 6, 7);
+            const f16x8 cv = __builtin_bit_cast(f16x8, ctx[(JT + jp) * 64 + lane]);          // {c (t0) | c (t1)}, rows 0..7 hi, 8..15 lo
+            u = __builtin_amdgcn_mfma_f32_16x16x32_f16(cv, plo, u, 0, 0, 0);
+            u = __builtin_amdgcn_mfma_f32_16x16x32_f16(cv, phi, u, 0, 0, 0);
+        }
+        float l = l2[0] + l2[1];
+        l += __shfl_xor(l, 16);
+        l += __shfl_xor(l, 32);
+        const float linv = 1.0f / l;
+        // u / l is a convex combination of context rows: same bound, same scaling 2^c_exp
+        f16x4 uh, ul;
+        {
+            const float un[4] = {u[0] * linv, u[1] * linv, u[2] * linv, u[3] * linv};
+            split_f16(un, uh, ul);
+        }
+        const f16x8 ub = __builtin_shufflevector(uh, ul, 0, 1, 2, 3, 4, 5, 6, 7);
+        oacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ht[3 * 64 + lane]), ub, oacc, 0, 0, 0);      // {MV lo | 0}
+        oacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ht[2 * 64 + lane]), ub, oacc, 0, 0, 0);      // {MV hi | MV hi}
+        const float w0 = __shfl(p0, lq) * linv;
+        const float4 v0 = __builtin_bit_cast(float4, ht[4 * 64 + lane]);
+        onull[0] = fmaf(w0, v0.x, onull[0]); onull[1] = fmaf(w0, v0.y, onull[1]);
+        onull[2] = fmaf(w0, v0.z, onull[2]); onull[3] = fmaf(w0, v0.w, onull[3]);
+    }
+    float o[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = ldexpf(oacc[r], -p.v_exp) + onull[r];
+
+    // to_out.1 LayerNorm + residual + statistics (as variant 6)
+    float yv[4] = {0.f, 0.f, 0.f, 0.f};
+    {
+        float s1 = o[0] + o[1] + o[2] + o[3];
+        s1 += __shfl_xor(s1, 16); s1 += __shfl_xor(s1, 32);
+        const float mean = s1 / (float)C;
+        float v = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { const int a = 4 * lg + r; const float d = (a < C) ? o[r] - mean : 0.0f; v = fmaf(d, d, v); }
+        v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+        const float rstd = 1.0f / sqrtf(v / (float)C + 1e-5f);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int a = 4 * lg + r;
+            if (a < C && ok) {
+                const float y = (o[r] - mean) * rstd * p.n2_g[a] + p.n2_b[a] + ldx(a) * p.x.scale;
+                p.out[((size_t)b * C + a) * p.HW + i] = y;
+                yv[r] = y;
+            }
+        }
+    }
+    if (p.out_stats) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int a = 4 * lg + r;
+            double S, Q;
+            mi_stat_reduce16(yv[r], a < C && ok, lane, S, Q);
+            if (lq == 0) { red[wave][2 * a] = S; red[wave][2 * a + 1] = Q; }
+        }
+        __syncthreads();
+        const int nt64 = (p.HW + 63) / 64;               // statistics tiles are 64 tokens = 4 waves, whatever the workgroup size
+        for (int sub = 0; sub < NWV / 4; ++sub) {
+            const int st = tile * (NWV / 4) + sub;
+            if (tid < 2 * C && st < nt64)
+                p.out_stats[((size_t)(b * C + (tid >> 1)) * nt64 + st) * 2 + (tid & 1)] =
+                    red[4 * sub][tid] + red[4 * sub + 1][tid] + red[4 * sub + 2][tid] + red[4 * sub + 3][tid];
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int mi_attn_cond_head_floats(void) { return MI_COND_HEAD_ROWS * 64 * 4; }
 
 extern "C" int mi_cross_attn_fwd(const mi_cross_attn_params* pp, void* stream) {
     const mi_cross_attn_params& p = *pp;
@@ -329,6 +555,17 @@ extern "C" int mi_cross_attn_fwd(const mi_cross_attn_params* pp, void* stream) {
         }
 #undef MI_ATTN16_LAUNCH
         return mi_check_launch("cross_attn_f16x3_kernel");
+    }
+    if (p.variant == 8) {       // 3-term split contracted over cond_dim (context fragments from mi_attn_cond_rows, head tables from the host)
+        if (JT != 17 || p.heads != 8 || (p.C != 8 && p.C != 16) || !p.head_tab) { mi_set_error("mi_cross_attn_fwd: variant 8 is instantiated for C in {8,16}, 8 heads, a 17-tile context and needs head_tab (C %d, heads %d, J %d)", p.C, p.heads, p.J); return MI_ERR_UNSUPPORTED; }
+        static const int force_nwv = getenv("MI_ATTN_WAVES") ? atoi(getenv("MI_ATTN_WAVES")) : 0;      // A/B knob: 8 or 16
+        const int nwv = (force_nwv == 8 || force_nwv == 16) ? force_nwv : (p.HW <= 1024 ? 16 : 8);       // variant 6's geometry
+        const dim3 g8(((p.HW + 16 * nwv - 1) / (16 * nwv)) * p.B2);
+        if (p.C == 8 && nwv == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(cross_attn_cond_f16x3_kernel<8, 8>), g8, dim3(512), 0, st, p);
+        else if (p.C == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(cross_attn_cond_f16x3_kernel<8, 16>), g8, dim3(1024), 0, st, p);
+        else if (nwv == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(cross_attn_cond_f16x3_kernel<16, 8>), g8, dim3(512), 0, st, p);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(cross_attn_cond_f16x3_kernel<16, 16>), g8, dim3(1024), 0, st, p);
+        return mi_check_launch("cross_attn_cond_f16x3_kernel");
     }
     mi_set_error("mi_cross_attn_fwd: variant %d (6 = 3-term fp16 split, fp32-grade; 7 = single fp16 term: the reduced-precision configuration)", p.variant);
     return MI_ERR_UNSUPPORTED;

@@ -53,6 +53,7 @@ extern "C" int mi_struct_size(int which) {
         case 24: return (int)sizeof(mi_sampler_ext_params);
         case 25: return (int)sizeof(mi_inpaint_params);
         case 26: return (int)sizeof(mi_init_down_params);
+        case 27: return (int)sizeof(mi_attn_cond_params);
     }
     return -1;
 }

@@ -215,7 +215,56 @@ __global__ __launch_bounds__(256) void attn_fold_rows_kernel(const mi_attn_fold_
     }
 }
 
+// context rows -> the head-independent operands of the cross-attention contracted over cond_dim (variant 8; layout in minimagen_hip.h)
+__global__ __launch_bounds__(256) void attn_cond_rows_kernel(const mi_attn_cond_params p) {
+    const int bb = blockIdx.x;
+    const int step = p.t_state ? *p.t_state - p.t_off : 0;
+    if (blockIdx.y == 1) {            // this step's scale/shift rows
+        const float* src = p.ss_all + ((size_t)step * gridDim.x + bb) * p.ss_n;
+        for (int i = threadIdx.x; i < p.ss_n; i += 256) p.ss[(size_t)bb * p.ss_n + i] = src[i];
+        return;
+    }
+    const int JP = (p.JT + 1) / 2;
+    _Float16* fb = reinterpret_cast<_Float16*>(p.frag) + (size_t)bb * (p.JT + JP) * 64 * 8;
+    const float* rows = p.c_rows + (size_t)(p.t_state ? step : bb) * p.c_stride_b;
+    const int first = p.write_null ? -1 : 0;
+    const int total = (p.nrows - first) * 9;
+    for (int idx = threadIdx.x; idx < total; idx += 256) {
+        const int d = idx % 9, r = idx / 9 + first;
+        const int j = r < 0 ? 0 : p.row0 + r;
+        const int jt = j >> 4, jm = j & 15;
+        _Float16* ts = fb + (size_t)jt * 64 * 8;
+        if (d == 8) {                  // the null indicator: exact, no lo half
+            const _Float16 ind = (_Float16)(r < 0 ? ldexpf(1.0f, p.i_exp) : 0.0f);
+            _Float16* l8 = ts + (size_t)(jm + 32) * 8;
+            l8[2] = ind;
+            l8[5] = ind;
+            continue;
+        }
+        const float c = (r < 0 || d >= p.cd) ? 0.0f : ldexpf(rows[(size_t)r * p.cd + d], p.c_exp);       // exact power-of-two scaling
+        const _Float16 hi = (_Float16)c, lo = (_Float16)(c - (float)hi);
+        _Float16* lh = ts + (size_t)(jm + 16 * (d / 3)) * 8;
+        lh[d % 3] = hi;
+        lh[3 + d % 3] = hi;
+        ts[(size_t)(jm + 16 * (d >> 1)) * 8 + 6 + (d & 1)] = lo;
+        _Float16* tv = fb + (size_t)(p.JT + (jt >> 1)) * 64 * 8 + (size_t)(16 * (jm >> 2)) * 8 + 4 * (jt & 1) + (jm & 3);
+        tv[(size_t)d * 8] = hi;
+        tv[(size_t)(d + 8) * 8] = lo;
+    }
+}
+
 }  // namespace
+
+extern "C" int mi_attn_cond_frag_floats(int JT) { return (JT + (JT + 1) / 2) * 64 * 4; }
+
+extern "C" int mi_attn_cond_rows(const mi_attn_cond_params* p, void* stream) {
+    if (p->B2 <= 0 || p->cd <= 0 || p->cd > 8 || p->JT <= 0 || !p->frag) { mi_set_error("mi_attn_cond_rows: cd %d (1 .. 8) / JT %d / empty batch", p->cd, p->JT); return MI_ERR_INVALID; }
+    if (p->row0 < 0 || p->nrows < 0 || p->row0 + p->nrows > p->JT * 16 || (p->nrows && (p->row0 < 1 || !p->c_rows))) { mi_set_error("mi_attn_cond_rows: rows beyond the padded context (row 0 is the null row)"); return MI_ERR_INVALID; }
+    if (p->i_exp < -14 || p->i_exp > 15) { mi_set_error("mi_attn_cond_rows: the indicator 2^%d is no normal fp16 number", p->i_exp); return MI_ERR_INVALID; }
+    if (p->ss_n > 0 && (!p->t_state || !p->ss_all || !p->ss)) { mi_set_error("mi_attn_cond_rows: the scale/shift copy needs t_state, ss_all and ss"); return MI_ERR_INVALID; }
+    hipLaunchKernelGGL(attn_cond_rows_kernel, dim3(p->B2, p->ss_n > 0 ? 2 : 1), dim3(256), 0, (hipStream_t)stream, *p);
+    return mi_check_launch("attn_cond_rows_kernel");
+}
 
 extern "C" int mi_attn_fragment_floats(int C) { return ((C / 4) < 4 ? 4 : (C / 4)) + 4 * ((C + 15) / 16); }
 

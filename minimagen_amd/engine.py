@@ -32,6 +32,7 @@ CONV_WIDE_GEMM = os.environ.get("MINIMAGEN_CONV_WIDE_GEMM", "1") != "0"   # wide
 COND_GEMM = int(os.environ.get("MINIMAGEN_COND_GEMM", "2048"))           # stacked time-MLPs with at least this many rows run as one GEMM per step (0 = always inside cond_step_kernel)
 FLASH_KV_PREP = os.environ.get("MINIMAGEN_FLASH_KV_PREP", "1") != "0"     # multi-query self-attention of the wide presets: K / V prepared once per launch, LDS-DMA into the workgroups
 CE_MFMA = os.environ.get("MINIMAGEN_CE_MFMA", "1") != "0"                  # CrossEmbed on the matrix cores (0: the fp32 VALU kernel)
+ATTN_COND = os.environ.get("MINIMAGEN_ATTN_COND", "1") != "0"              # folded cross-attention contracted over cond_dim (variant 8: C in {8, 16}, cond_dim <= 8, fp32); 0: variant 6 with its per-head fragments and step tables
 INIT_DOWN = os.environ.get("MINIMAGEN_INIT_DOWN", "1") != "0"              # CrossEmbed + the first level's pre-Downsample as one launch (0: the two launches)
 CONV_REVERSE = int(os.environ.get("MINIMAGEN_CONV_REVERSE", "1"))        # a row-paired conv walks the image groups opposite to its producer (0 = off)
 RP_NTILE = int(os.environ.get("MINIMAGEN_RP_NTILE", "0"))               # tiles per workgroup of the row-paired kernel (0 = the library's choice)
@@ -223,6 +224,7 @@ class UnetEngine:
         pk.conv_ig = {}
         pk.attn = {}
         pk.attn_exp = {}
+        pk.attn_cond = {}      # variant 8: id(ca) -> (exponents, per-head tables)
 
         def conv_pack(mod: nn.Conv2d, w=None, b=None):
             w = mod.weight if w is None else w
@@ -277,6 +279,12 @@ class UnetEngine:
                 # power-of-two operand scalings of the fp16x3 kernel from magnitude bounds of its inputs (both are LayerNorm outputs)
                 pk.attn_exp[id(ca)] = P.attn_f16_exponents(mg, mv, g0, v0, cmax=P.layernorm_bound(u.norm_cond.weight, u.norm_cond.bias, u.cond_dim),
                                                            xmax=P.layernorm_bound(ca.norm.gamma, ca.norm.beta, Cc))
+                if ATTN_COND and Cc in (8, 16) and u.cond_dim <= 8 and ca.heads == 8:
+                    # the same contractions over cond_dim: exponents from the same bounds, per-head tables from the weights alone
+                    ex = P.attn_cond_exponents(mg, mv, g0, v0, cmax=P.layernorm_bound(u.norm_cond.weight, u.norm_cond.bias, u.cond_dim),
+                                               xmax=P.layernorm_bound(ca.norm.gamma, ca.norm.beta, Cc))
+                    if ex is not None:
+                        pk.attn_cond[id(ca)] = (ex, P.pack_cross_attn_cond(mg, mv, g0, v0, ex["f_exp"], ex["g0_exp"], ex["mv_exp"]))
         # K10: multi-query self-attention (one shared 64-wide k/v head, layers.py:42) folded like K9 with the k/v rows repeated per head
         for m in u.modules():
             if isinstance(m, Attention):
@@ -387,6 +395,7 @@ class UnetEngine:
         # (row-paired convs, matrix-core CrossEmbed, fp16 cross-attention: the BASELINE U-Nets); otherwise fp32 storage
         for store16 in ((True, False) if ws.half else (False,)):
             ws.store16 = store16
+            ws.cfrag = None
             ws.gv, ws.tensors, ws.prog, ws.prog_text, ws.wide_attn = {}, [], [], [], False     # (prog_text: the wide cross-attentions' text keys / values)
             ws.ig_convs = []                 # wide GEMM convs: their operand planes share ONE buffer (the launches of a workspace are ordered)
             try:
@@ -672,10 +681,18 @@ class UnetEngine:
         Cc, HW = h.C, h.H * h.W
         if Cc not in (8, 16, 32):
             return self._emit_cross_attn_wide(ws, ca, h)
-        FR = lib.mi_attn_fragment_floats(Cc)
-        jts = ws.JT + (ws.JT & 1)            # fp16 fragments: V chunks live per PAIR of context tiles
-        gv = torch.zeros(ws.B2, ca.heads, jts, 64, FR, dtype=torch.float32, device=ws.dev)        # zero-filled: padded context rows must read as finite
-        ws.gv[id(ca)] = gv
+        cond = pk.attn_cond.get(id(ca)) if (not ws.half and ws.JT == 17) else None       # variant 8: fp32, the text context; else variants 6 / 7
+        if cond is not None:
+            if ws.cfrag is None:             # ONE set of context fragments per batch row: no head, no block in them
+                ws.cfrag = torch.zeros(ws.B2, lib.mi_attn_cond_frag_floats(ws.JT), dtype=torch.float32, device=ws.dev)     # zero-filled: padded rows must read as finite
+                ws.cfrag_exp = (cond[0]["c_exp"], cond[0]["i_exp"])
+            assert ws.cfrag_exp == (cond[0]["c_exp"], cond[0]["i_exp"])
+            gv = ws.cfrag
+        else:
+            FR = lib.mi_attn_fragment_floats(Cc)
+            jts = ws.JT + (ws.JT & 1)            # fp16 fragments: V chunks live per PAIR of context tiles
+            gv = torch.zeros(ws.B2, ca.heads, jts, 64, FR, dtype=torch.float32, device=ws.dev)        # zero-filled: padded context rows must read as finite
+            ws.gv[id(ca)] = gv
         nt = -(-HW // 64)
         out = self._new_act(ws, ws.B2, Cc, h.H, h.W, nt)
         p = L.MiCrossAttnParams()
@@ -687,6 +704,10 @@ class UnetEngine:
         p.out_st = out.st
         p.out, p.out_stats, p.variant = L.ptr(out.t), L.ptr(out.stats), (7 if ws.half else 6)       # 3-term fp16 split (fp32-grade) / single term
         p.x_exp, p.g_exp, p.v_exp = pk.attn_exp[id(ca)]
+        if cond is not None:
+            ex, tab = cond
+            p.variant, p.head_tab = 8, L.ptr(tab)
+            p.x_exp, p.g_exp, p.v_exp = ex["x_exp"], ex["f_exp"] + ex["c_exp"], ex["c_exp"] + ex["mv_exp"]
         ws.prog.append((lib.mi_cross_attn_fwd, p, "cross_attn"))
         return out
 
@@ -768,6 +789,13 @@ class UnetEngine:
                     p.blk[k].mg, p.blk[k].mv, p.blk[k].g0, p.blk[k].v0 = L.ptr(mg), L.ptr(mv), L.ptr(g0), L.ptr(v0)
                     p.blk[k].gv = L.ptr(ws.gv[cid])
                 calls.append((lib.mi_attn_fold_rows, p, "fold"))
+        if ws.cfrag is not None:          # variant 8: the head-independent context fragments, shared by its blocks
+            p = L.MiAttnCondParams()
+            p.B2, p.cd, p.JT = ws.B2, self.unet.cond_dim, ws.JT
+            p.c_rows, p.c_stride_b, p.row0, p.nrows, p.write_null = L.ptr(rows_t), stride_b, row0, nrows, write_null
+            p.c_exp, p.i_exp = ws.cfrag_exp
+            p.frag = L.ptr(ws.cfrag)
+            calls.append((lib.mi_attn_cond_rows, p, "fold_cond"))
         return calls
 
     def _build_program(self, ws, pk):
@@ -908,7 +936,7 @@ class UnetEngine:
         if (out.H, out.W) != (H, W):
             raise L.MinImagenHipError(f"U-Net output is {out.H}x{out.W} for a {H}x{W} input (image size must be divisible by the down-sampling factor)")
         # time-token rows of the folded context, every step
-        if ws.gv:
+        if ws.gv or ws.cfrag is not None:
             ws.prog_cond += self._fold_params(ws, pk, ws.c_time, ws.ntot * u.cond_dim, 1, ws.ntot, 0)
 
     # ------------------------------------------------------------------ execution
@@ -999,6 +1027,11 @@ class UnetEngine:
             tb.fold, tb.tables = [], []
             stage_blocks = []
             for fn, fp, name in self._fold_params(ws, pk, tb.c_time_t, ws.ntot * u.cond_dim, 1, ws.ntot, 0):
+                if isinstance(fp, L.MiAttnCondParams):                     # variant 8: the step's rows of c_time_t go straight into the fragments, no folded table
+                    f2 = L.MiAttnCondParams.from_buffer_copy(fp)
+                    f2.t_state = L.ptr(t_state)
+                    stage_blocks.append(f2)
+                    continue
                 f1 = L.MiAttnFoldParams.from_buffer_copy(fp)
                 f1.B2, f1.mode = T, 1
                 for k in range(fp.n_blocks):
@@ -1014,7 +1047,7 @@ class UnetEngine:
                 f2.B2, f2.mode, f2.t_state, f2.n_blocks = B2, 3, L.ptr(t_state), 0
                 stage_blocks.append(f2)
             stage_blocks[0].ss_all, stage_blocks[0].ss, stage_blocks[0].ss_n = L.ptr(tb.ss), L.ptr(ws.ss), ws.ss.shape[1]
-            tb.stage = [(lib.mi_attn_fold_rows, f2, "stage_step") for f2 in stage_blocks]
+            tb.stage = [(lib.mi_attn_cond_rows if isinstance(f2, L.MiAttnCondParams) else lib.mi_attn_fold_rows, f2, "stage_step") for f2 in stage_blocks]
             tb.keep = t_state
             ws.step_tables[key] = tb
         tb.text_hiddens.view(T, B2, -1).copy_(ws.text_hiddens.unsqueeze(0).expand(T, -1, -1))
@@ -1051,7 +1084,7 @@ class UnetEngine:
         if key not in cache:
             prog = []
             for fn, p, name in ws.prog_stage:
-                q = L.MiAttnFoldParams.from_buffer_copy(p)
+                q = type(p).from_buffer_copy(p)
                 q.t_off = t_off
                 prog.append((fn, q, name))
             cache[key] = prog

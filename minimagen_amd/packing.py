@@ -155,6 +155,77 @@ def attn_f16_exponents(mg, mv, g0, v0, cmax: float, xmax: float):
     return k(xmax), k(gb), k(vb)
 
 
+def attn_cond_exponents(mg, mv, g0, v0, cmax: float, xmax: float):
+    """Power-of-two operand scalings of the cross-attention contracted over cond_dim (variant 8), from the same magnitude BOUNDS and with
+    the same <= 2^12 landing rule as attn_f16_exponents.  Returns a dict, or None where the operands cannot be placed (the caller keeps
+    variant 6):
+      x_exp   LayerNorm(x), |x^| <= xmax
+      c_exp   context rows, |c| <= cmax; u / l is a convex combination of context rows, so it shares bound and exponent
+      i_exp   the null key's indicator 2^i_exp (a normal fp16 number as close to the context scale as the format allows)
+      f_exp   the y~ functionals MG_h^T -- chosen so that BOTH the functionals and y~ = F x^ (|y~| <= column sums of |MG| * xmax) land at
+              <= 2^12 with the ONE scaling 2^(f_exp + x_exp): the kernel splits y~ as it leaves the accumulators, no multiplication
+      g0_exp  the g0 row of the functionals: f_exp + c_exp - i_exp, so that the null score carries the other scores' 2^(x_exp + f_exp + c_exp)
+      mv_exp  MV_h
+    c_exp and i_exp depend on norm_cond alone: every cross-attention block of a U-Net shares one set of context fragments."""
+    def k(bound):
+        bound = float(bound)
+        if not math.isfinite(bound) or bound <= 0.0:
+            return 0
+        return max(-40, min(40, 12 - math.ceil(math.log2(bound))))
+    x_exp, c_exp = k(xmax), k(cmax)
+    i_exp = max(-14, min(12, c_exp))
+    shift = c_exp - i_exp                      # the g0 row carries what the indicator cannot
+    mgd, g0d = mg.detach().double(), g0.detach().double()
+    f_exp = min(k(float(mgd.abs().max())), k(float(mgd.abs().sum(1).max()) * xmax) - x_exp)
+    g0_exp = min(k(float(g0d.abs().max())), k(float(g0d.abs().sum(-1).max()) * xmax) - x_exp)
+    f_exp = min(f_exp, g0_exp - shift)
+    g0_exp = f_exp + shift
+    mv_exp = k(float(mv.detach().abs().max()))
+    if max(abs(e) for e in (x_exp, c_exp, f_exp, g0_exp, mv_exp)) > 60:
+        return None
+    return dict(x_exp=x_exp, c_exp=c_exp, i_exp=i_exp, f_exp=f_exp, g0_exp=g0_exp, mv_exp=mv_exp)
+
+
+def pack_cross_attn_cond(mg, mv, g0, v0, f_exp: int, g0_exp: int, mv_exp: int):
+    """Per-head tables of the cross-attention contracted over cond_dim (csrc/attention.hip, variant 8): weights only, packed once.
+    mg, mv [H][C][cd], g0, v0 [H][C] (fold_cross_attention), C <= 16, cd <= 8.  Returns float32 [H][5][64 lanes][4] holding, per head,
+    five MFMA A operands of 16 bytes per lane (lane = 16 lg + lq):
+      0, 1  F tile T: row m = lq is the functional of K slot (lg' = m >> 2, e = 4T + (m & 3)) of the score instruction -- e = 0..2 and 3..5:
+            d = 3lg' + e mod 3, e = 6, 7: d = 2lg' + e - 6; d < 8: MG_h[:, d] * 2^f_exp, d = 8: g0_h * 2^g0_exp, else 0 -- as
+            {4 hi | 4 lo} of channels a = 4lg + e'
+      2     {MV hi | MV hi}[a = lq][d = (4lg + e') mod 8] * 2^mv_exp: the duplicated columns add the c hi and c lo halves of u
+      3     {MV lo | 0}
+      4     v0_h[4lg .. 4lg + 3] as fp32"""
+    H, Cc, cd = mg.shape
+    assert Cc <= 16 and cd <= 8
+    dev = mg.device
+    F = torch.zeros(H, 12, 16, dtype=torch.float64)
+    F[:, :cd, :Cc] = mg.detach().double().cpu().transpose(1, 2) * 2.0 ** f_exp
+    F[:, 8, :Cc] = g0.detach().double().cpu() * 2.0 ** g0_exp
+    MV = torch.zeros(H, 16, 8, dtype=torch.float64)
+    MV[:, :Cc, :cd] = mv.detach().double().cpu() * 2.0 ** mv_exp
+    V0 = torch.zeros(H, 16, dtype=torch.float32)
+    V0[:, :Cc] = v0.detach().float().cpu()
+    lane = torch.arange(64)
+    lq, lg = lane & 15, lane >> 4
+    el = torch.arange(4)
+    a = 4 * lg[:, None] + el[None, :]                                    # [64][4]
+    split = lambda t: (t.float().half(), (t - t.float().half().double()).float().half())
+    rows = []
+    for T in range(2):
+        e = 4 * T + (lq & 3)
+        lgp = lq >> 2
+        d = torch.where(e < 6, 3 * lgp + e % 3, 2 * lgp + e - 6)        # [64]
+        hi, lo = split(F[:, d[:, None], a])                              # [H][64][4]
+        rows.append(torch.cat((hi, lo), -1))
+    hi, lo = split(MV[:, lq[:, None], a % 8])
+    rows.append(torch.cat((hi, hi), -1))
+    rows.append(torch.cat((lo, torch.zeros_like(lo)), -1))
+    rows.append(V0[:, a].contiguous().view(torch.float16))              # [H][64][8] halves = 4 floats
+    tab = torch.stack(rows, 1).contiguous()                              # [H][5][64][8] fp16
+    return tab.view(torch.float32).contiguous().to(dev)
+
+
 def layernorm_bound(weight, bias, n: int) -> float:
     """max |LayerNorm(x)_i| over any input: a normalised element is at most sqrt(n - 1) in magnitude"""
     with torch.no_grad():           # ONE device -> host copy for both maxima
