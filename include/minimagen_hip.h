@@ -714,6 +714,28 @@ typedef struct {
 } mi_adam_params;
 int mi_adam_step(const mi_adam_params* p, void* stream);
 
+/* ---- exponential moving average of the weights, in the launch geometry of mi_adam_step ------------------------------------
+ * One mi_ema_tensor per parameter: its fp32 shadow `e`, the parameter `p`, `n` elements; `tensors`, `chunk_tensor`, `chunk_off` are DEVICE
+ * arrays as in mi_adam_params.  w = 1 - decay, formed in double by the host; w == 1 copies p exactly.
+ *   mi_ema_update     e <- fmaf(p - e, w, e) for every element
+ *   mi_adam_ema_step  mi_adam_step(a) with the same lerp on the new p inside the launch: p, m, v, e come out with the bits of mi_adam_step
+ *                     followed by mi_ema_update.  e->tensors is ROW-PARALLEL to a->tensors (row k shadows a->tensors[k], same n); the chunk
+ *                     list is a's, e's own chunk fields are not read
+ *   mi_ema_swap       exchanges p and e as 32-bit words (NaN payloads and -0.0 survive; two swaps are the identity); w is not read
+ * MI_ERR_INVALID for empty / missing tables and for w outside [0, 1].  Struct indices 28 and 29 of mi_struct_size; added within ABI 12 (no
+ * existing struct or entry changed). */
+typedef struct { float* e; float* p; long long n; } mi_ema_tensor;
+typedef struct {
+    const mi_ema_tensor* tensors;
+    const int* chunk_tensor; const int* chunk_off;
+    int nchunks, chunk;
+    float w;
+    int reserved;
+} mi_ema_params;
+int mi_ema_update(const mi_ema_params* p, void* stream);
+int mi_adam_ema_step(const mi_adam_params* a, const mi_ema_params* e, void* stream);
+int mi_ema_swap(const mi_ema_params* p, void* stream);
+
 /* ---- HIP graphs: capture a sequence of the calls above once, replay it per timestep ------- */
 int mi_graph_begin(void* stream);
 int mi_graph_end(void* stream, void** graph_exec);

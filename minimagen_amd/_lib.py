@@ -212,6 +212,15 @@ class MiAdamParams(C.Structure):
                 ("grad_scale", C.c_void_p)]
 
 
+class MiEmaTensor(C.Structure):
+    _fields_ = [("e", C.c_void_p), ("p", C.c_void_p), ("n", C.c_longlong)]
+
+
+class MiEmaParams(C.Structure):
+    _fields_ = [("tensors", C.c_void_p), ("chunk_tensor", C.c_void_p), ("chunk_off", C.c_void_p), ("nchunks", C.c_int), ("chunk", C.c_int),
+                ("w", C.c_float), ("reserved", C.c_int)]
+
+
 class MiPackConv3Desc(C.Structure):
     _fields_ = [("w", C.c_void_p), ("frag", C.c_void_p), ("generic", C.c_void_p), ("Cout", C.c_int), ("Cin", C.c_int), ("adjoint", C.c_int),
                 ("exp", C.c_int), ("cout_pad", C.c_int), ("reserved", C.c_int)]
@@ -220,7 +229,8 @@ class MiPackConv3Desc(C.Structure):
 _STRUCTS = {0: MiAct, 1: MiConvParams, 2: MiCrossEmbedParams, 3: MiLinear, 4: MiTextCondParams, 5: MiCondStepParams,
             6: MiAttnFoldParams, 7: MiCrossAttnParams, 8: MiCfgX0Params, 9: MiQuantileParams, 10: MiPosteriorParams,
             11: MiResizeParams, 12: MiSelfAttnParams, 13: MiChanFFParams, 14: MiFlashAttnParams, 15: MiTokensToNchwParams, 16: MiConvWgradParams, 17: MiBlockBwdParams, 18: MiCrossEmbedWgradParams, 19: MiFoldedAttnParams, 20: MiAdamTensor, 21: MiAdamParams, 22: MiPackConv3Desc,
-            23: MiFlashAttnTrainParams, 24: MiSamplerExtParams, 25: MiInpaintParams, 26: MiInitDownParams, 27: MiAttnCondParams}
+            23: MiFlashAttnTrainParams, 24: MiSamplerExtParams, 25: MiInpaintParams, 26: MiInitDownParams, 27: MiAttnCondParams,
+            28: MiEmaTensor, 29: MiEmaParams}
 
 _lib = None
 _backend = None
@@ -239,9 +249,11 @@ def _bind(lib):
     for name in ("mi_conv_fwd", "mi_gn_coef_fwd", "mi_crossembed_fwd", "mi_text_cond_fwd", "mi_cond_step_fwd", "mi_attn_fold_rows", "mi_cross_attn_fwd",
                  "mi_cfg_x0_fwd", "mi_quantile_fwd", "mi_posterior_fwd", "mi_resize_fwd", "mi_self_attn_fwd", "mi_chan_ff_fwd",
                  "mi_flash_attn_fwd", "mi_conv_prep_fwd", "mi_tokens_to_nchw_fwd", "mi_conv_wgrad", "mi_block_bwd", "mi_crossembed_wgrad", "mi_folded_attn_fwd", "mi_folded_attn_bwd", "mi_adam_step",
-                 "mi_flash_attn_train_fwd", "mi_flash_attn_train_bwd", "mi_init_down_fwd", "mi_attn_cond_rows"):
+                 "mi_flash_attn_train_fwd", "mi_flash_attn_train_bwd", "mi_init_down_fwd", "mi_attn_cond_rows", "mi_ema_update", "mi_ema_swap"):
         getattr(lib, name).argtypes = [vp, vp]
         getattr(lib, name).restype = i32
+    lib.mi_adam_ema_step.argtypes = [vp, vp, vp]
+    lib.mi_adam_ema_step.restype = i32
     lib.mi_conv_prep_bytes.argtypes = [i32, i32, i32, i32, i32]
     lib.mi_conv_prep_bytes.restype = C.c_longlong
     lib.mi_flash_kv_prep_bytes.argtypes = [i32, i32]

@@ -54,6 +54,8 @@ extern "C" int mi_struct_size(int which) {
         case 25: return (int)sizeof(mi_inpaint_params);
         case 26: return (int)sizeof(mi_init_down_params);
         case 27: return (int)sizeof(mi_attn_cond_params);
+        case 28: return (int)sizeof(mi_ema_tensor);
+        case 29: return (int)sizeof(mi_ema_params);
     }
     return -1;
 }

@@ -1,6 +1,6 @@
 """The reference's training driver surface (minimagen/training.py) over the device training path: command-line parser, training /
 validation loop with its on-disk layout, and the helpers train.py calls.  What is kept is the OBSERVABLE behaviour -- flag names and defaults,
-``training_<timestamp>/{parameters,state_dicts,tmp}``, ``training_progess.txt`` [sic] and its lines, the checkpoint file names
+``training_<timestamp>/{parameters,state_dicts,tmp}`` (plus ``ema_tmp`` / ``ema_state_dicts`` when the loop is given an EMA), ``training_progess.txt`` [sic] and its lines, the checkpoint file names
 ``minimagen_amd.generate.load_minimagen`` reads back.  The reference's ``train.py`` does NOT run unchanged against this package: it calls
 ``ConceptualCaptions`` unconditionally (train.py:43-47; a network download, SURVEY 2: out of scope) and that raises here, and the
 reference's ``MinimagenDataset`` / ``_Rescale`` are not rebuilt.  Everything else train.py imports from ``minimagen.training`` resolves;
@@ -140,25 +140,44 @@ def _save_tmp(training_dir, imagen, n_unets):
             torch.save(imagen.unets[i].state_dict(), f"unet_{i}_tmp.pth")
 
 
-def MinimagenTrain(timestamp, args, unets, imagen, train_dataloader, valid_dataloader, training_dir, optimizer, timeout=60, fail_fast=False):
+def _save_ema(training_dir, imagen, n_unets, ema):
+    """inside ``ema.average_parameters()``: the averaged U-Nets (buffers from the live model) and the EMA's own state, in ``ema_tmp/``
+    (``EMA.state_dict()`` gives the averages inside the block too: ``ema_state.pth`` holds the parameters of the files next to it)"""
+    with training_dir():
+        os.makedirs("ema_tmp", exist_ok=True)               # (created on demand: a directory of a run without EMA has no such folder)
+    with training_dir("ema_tmp"):
+        for i in range(n_unets):
+            torch.save(imagen.unets[i].state_dict(), f"unet_{i}_tmp.pth")
+        torch.save(ema.state_dict(), "ema_state.pth")
+
+
+def MinimagenTrain(timestamp, args, unets, imagen, train_dataloader, valid_dataloader, training_dir, optimizer, timeout=60, fail_fast=False, *,
+                   ema=None):
     """training.py:344-478.  Per batch: for every U-Net of the cascade ``imagen(images, text_embeds, text_masks, unet_number)`` ->
     ``backward`` -> gradient-norm clip at 50 over ALL parameters; optimiser step every ACCUM_ITER batches (and at the last batch); every
     CHCKPT_NUM batches: rolling checkpoints in ``tmp/``, running / batch losses, a validation pass, best-so-far state dicts in ``state_dicts/``.
     A batch that raises leaves a note and the latest state dicts in ``tmp/`` and the loop goes on with the next batch, as the reference's
-    does (``fail_fast=True``, not in the reference, re-raises instead); one that exceeds ``timeout`` seconds is skipped."""
+    does (``fail_fast=True``, not in the reference, re-raises instead); one that exceeds ``timeout`` seconds is skipped.
+
+    ``ema`` (not in the reference): a ``minimagen_amd.optim.EMA`` over ``imagen``.  It is attached to ``optimizer`` when that is an
+    ``optim.Adam`` (the shadow update rides in the Adam launch), otherwise updated after every ``optimizer.step()``.  Every checkpoint then
+    also writes the averaged U-Nets to ``ema_tmp/unet_<i>_tmp.pth`` and the EMA's state to ``ema_tmp/ema_state.pth``, validates a second time
+    on the averaged weights (``... (EMA)`` lines in the progress file) and keeps the best averaged U-Nets in
+    ``ema_state_dicts/unet_<k>_state_<timestamp>.pth`` -- what ``generate.load_minimagen(directory, ema=True)`` reads.  ``tmp/`` and
+    ``state_dicts/`` hold what they hold without it."""
     n = len(unets)
     best = [torch.tensor(9999999.) for _ in range(n)]
+    best_ema = [torch.tensor(9999999.) for _ in range(n)]
     params = [p for p in imagen.parameters()]
+    ema_fused = False
+    if ema is not None:
+        from .optim import Adam as _Adam
+        ema_fused = isinstance(optimizer, _Adam)
+        if ema_fused:
+            ema.attach(optimizer)
 
-    def validate(epoch, batch_num, running, losses):
-        _progress(training_dir, f'{"-" * 10}Checkpoint created at batch number {batch_num}{"-" * 10}\n')
-        _save_tmp(training_dir, imagen, n)
-        avg = [r / max(batch_num, 1) for r in running]
-        _progress(training_dir, f"U-Nets Avg Train Losses Epoch {epoch + 1} Batch {batch_num}: {[round(float(v), 3) for v in avg]}\n"
-                                f"U-Nets Batch Train Losses Epoch {epoch + 1} Batch {batch_num}: {[round(float(v), 3) for v in losses]}\n")
-        imagen.train(False)
+    def valid_losses(tag=""):
         vsum = [0. for _ in range(n)]
-        print(f'\n{"-" * 10}Validation...{"-" * 10}')
         with torch.no_grad():
             for vb in valid_dataloader:
                 if not vb:
@@ -167,13 +186,38 @@ def MinimagenTrain(timestamp, args, unets, imagen, train_dataloader, valid_datal
                     vsum[k] = vsum[k] + imagen(vb["image"], text_embeds=vb["encoding"], text_masks=vb["mask"], unet_number=k + 1).detach()
         vavg = [torch.as_tensor(v / max(len(valid_dataloader), 1)).cpu() for v in vsum]
         for k, v in enumerate(vavg):
-            print(f"Unet {k} avg validation loss: ", v)
+            print(f"Unet {k} avg validation loss{tag}: ", v)
+        return vavg
+
+    def validate(epoch, batch_num, running, losses):
+        _progress(training_dir, f'{"-" * 10}Checkpoint created at batch number {batch_num}{"-" * 10}\n')
+        _save_tmp(training_dir, imagen, n)
+        avg = [r / max(batch_num, 1) for r in running]
+        _progress(training_dir, f"U-Nets Avg Train Losses Epoch {epoch + 1} Batch {batch_num}: {[round(float(v), 3) for v in avg]}\n"
+                                f"U-Nets Batch Train Losses Epoch {epoch + 1} Batch {batch_num}: {[round(float(v), 3) for v in losses]}\n")
+        imagen.train(False)
+        print(f'\n{"-" * 10}Validation...{"-" * 10}')
+        vavg = valid_losses()
+        for k, v in enumerate(vavg):
             if v < best[k]:
                 best[k] = v
                 with training_dir("state_dicts"):
                     torch.save(imagen.unets[k].state_dict(), f"unet_{k}_state_{timestamp}.pth")
         _progress(training_dir, f"U-Nets Avg Valid Losses: {[round(float(v), 3) for v in vavg]}\n"
                                 f"U-Nets Best Valid Losses: {[round(float(v), 3) for v in best]}\n\n")
+        if ema is not None:                                 # the same pass on the averaged weights; one exchange in, one out per checkpoint
+            with ema.average_parameters():
+                _save_ema(training_dir, imagen, n, ema)
+                eavg = valid_losses(" (EMA)")
+                for k, v in enumerate(eavg):
+                    if v < best_ema[k]:
+                        best_ema[k] = v
+                        with training_dir():
+                            os.makedirs("ema_state_dicts", exist_ok=True)
+                        with training_dir("ema_state_dicts"):
+                            torch.save(imagen.unets[k].state_dict(), f"unet_{k}_state_{timestamp}.pth")
+            _progress(training_dir, f"U-Nets Avg Valid Losses (EMA): {[round(float(v), 3) for v in eavg]}\n"
+                                    f"U-Nets Best Valid Losses (EMA): {[round(float(v), 3) for v in best_ema]}\n\n")
         imagen.train(True)
 
     for epoch in range(args.EPOCHS):
@@ -196,6 +240,8 @@ def MinimagenTrain(timestamp, args, unets, imagen, train_dataloader, valid_datal
                         torch.nn.utils.clip_grad_norm_(params, 50)
                     if args.ACCUM_ITER == 1 or (batch_num % args.ACCUM_ITER == 0) or (batch_num + 1 == len(train_dataloader)):
                         optimizer.step()
+                        if ema is not None and not ema_fused:
+                            ema.update()
                         optimizer.zero_grad()
                     if batch_num % args.CHCKPT_NUM == 0:
                         validate(epoch, batch_num, running, losses)
