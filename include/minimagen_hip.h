@@ -702,7 +702,8 @@ long long mi_flash_attn_train_workspace(int B, int n, int heads, int kv_heads, i
  * (reference: train.py:99-100, training.py:375-377).  `tensors`, `chunk_tensor`, `chunk_off` are DEVICE arrays: one mi_adam_tensor per
  * parameter, and one (tensor index, chunk offset) pair per launched workgroup (chunk k of a tensor covers elements [k * chunk, (k + 1) * chunk)).
  * bias_correction1/2 = 1 - beta^step (computed by the host: the step count is host state, as in torch); grad_scale: optional device scalar every
- * gradient is multiplied by (a clipping coefficient computed on the device), or NULL. */
+ * gradient is multiplied by (a clipping coefficient computed on the device: out + 1 of mi_grad_clip_coef below), or NULL.
+ * g is read-only for every entry except mi_grad_scale, which writes through it. */
 typedef struct { float* p; const float* g; float* m; float* v; long long n; } mi_adam_tensor;
 typedef struct {
     const mi_adam_tensor* tensors;
@@ -713,6 +714,23 @@ typedef struct {
     const float* grad_scale;
 } mi_adam_params;
 int mi_adam_step(const mi_adam_params* p, void* stream);
+
+/* ---- gradient-norm clip on the device, over the table of mi_adam_step; added within ABI 12 (no struct added or changed) ------
+ * torch.nn.utils.clip_grad_norm_'s 2-norm and coefficient (reference: training.py:363-377), accumulated in fp64, no atomics: the same bits
+ * whatever order the workgroups run in.  Deferred form: sumsq -> clip_coef -> mi_adam_step / mi_adam_ema_step with grad_scale = out + 1
+ * (the gradients are never rewritten); in place: sumsq -> clip_coef -> mi_grad_scale.
+ *
+ * partials[c] = sum of g*g over chunk c of a's chunk list, accumulated in fp64.  Reads tensors[].g, tensors[].n and the chunk list only:
+ * p / m / v may be NULL and no scalar field of `a` is read.  partials: a->nchunks doubles on the device. */
+int mi_grad_sumsq(const mi_adam_params* a, double* partials, void* stream);
+/* S = partials[0] + ... + partials[n-1] (fixed order) + (extra ? *extra : 0), all fp64, on the device.
+ * out[0] = (float) sqrt(S)                                  -- the total norm before clipping
+ * out[1] = S is NaN ? NaN : (float) min(1.0, (double) max_norm / (sqrt(S) + 1e-6))   -- torch's clip coefficient, eps 1e-6, clamp at 1
+ * n == 0 is allowed when extra != NULL.  MI_ERR_INVALID: NULL out, n < 0, n > 0 with NULL partials, nothing to sum, max_norm negative or NaN. */
+int mi_grad_clip_coef(const double* partials, long long n, const double* extra, float max_norm, float* out, void* stream);
+/* g <- g * *a->grad_scale in place for every tensor of the table (the one entry that writes through mi_adam_tensor.g).  A workgroup that
+ * reads exactly 1.0f returns without loading or storing a gradient.  MI_ERR_INVALID without grad_scale. */
+int mi_grad_scale(const mi_adam_params* a, void* stream);
 
 /* ---- exponential moving average of the weights, in the launch geometry of mi_adam_step ------------------------------------
  * One mi_ema_tensor per parameter: its fp32 shadow `e`, the parameter `p`, `n` elements; `tensors`, `chunk_tensor`, `chunk_off` are DEVICE

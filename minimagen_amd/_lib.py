@@ -254,6 +254,11 @@ def _bind(lib):
         getattr(lib, name).restype = i32
     lib.mi_adam_ema_step.argtypes = [vp, vp, vp]
     lib.mi_adam_ema_step.restype = i32
+    lib.mi_grad_sumsq.argtypes = [vp, vp, vp]
+    lib.mi_grad_clip_coef.argtypes = [vp, C.c_longlong, vp, f32, vp, vp]
+    lib.mi_grad_scale.argtypes = [vp, vp]
+    for name in ("mi_grad_sumsq", "mi_grad_clip_coef", "mi_grad_scale"):
+        getattr(lib, name).restype = i32
     lib.mi_conv_prep_bytes.argtypes = [i32, i32, i32, i32, i32]
     lib.mi_conv_prep_bytes.restype = C.c_longlong
     lib.mi_flash_kv_prep_bytes.argtypes = [i32, i32]

@@ -6,6 +6,9 @@
 // in that operation order and in fp32 like ATen's kernels; HBM-bound (16 bytes read, 12 written per element).
 // Exponential moving average of the weights, same launch geometry: e <- e + (p - e) (1 - decay), alone (mi_ema_update), inside the
 // Adam launch on the new p (mi_adam_ema_step: the same bits as the two launches), and the exchange of p and e (mi_ema_swap).
+// Gradient-norm clip (the reference: training.py:363-377 clip_grad_norm_(params, 50)), same tables: per-chunk sums of squares in
+// fp64 (mi_grad_sumsq), a one-workgroup finish that writes the norm and torch's coefficient (mi_grad_clip_coef), and either the in-place
+// scaling (mi_grad_scale) or nothing at all -- adam_kernel / adam_ema_kernel read the coefficient through grad_scale.
 #include "common.hip.h"
 
 namespace {
@@ -75,6 +78,86 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(const mi_ema_params a) {
     }
 }
 
+// sum of g*g over one chunk, in fp64 from the first element (an fp32 square overflows above |g| = 1.8e19 and vanishes below 1e-23; the kernel
+// is its read stream either way).  Two accumulators per thread: the fp64 fma chain of 16 elements would otherwise serialise.  16-byte loads
+// when the chunk's first element is 16-byte aligned (an allocator's base + a multiple of 4096 elements), adam_kernel's dword loop otherwise
+// (a sliced gradient such as buf[1:]) and for the tail.  No atomics: partials[c] depends on chunk c alone, in a fixed order.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const mi_adam_params a, double* partials) {
+    __shared__ double red[4];
+    const int c = blockIdx.x;
+    const mi_adam_tensor t = a.tensors[a.chunk_tensor[c]];
+    const long long i0 = (long long)a.chunk_off[c] * a.chunk;
+    const long long i1 = i0 + a.chunk < t.n ? i0 + a.chunk : t.n;
+    double s0 = 0.0, s1 = 0.0;
+    long long i = i0;
+    if (i0 < i1 && (reinterpret_cast<size_t>(t.g + i0) & 15) == 0) {
+        const long long nv = (i1 - i0) >> 2;
+#pragma unroll 4
+        for (long long k = threadIdx.x; k < nv; k += 256) {
+            const float4 u = mi_ldg4(t.g + i0 + 4 * k);
+            const double x = (double)u.x, y = (double)u.y, z = (double)u.z, w = (double)u.w;
+            s0 = fma(x, x, s0); s1 = fma(y, y, s1); s0 = fma(z, z, s0); s1 = fma(w, w, s1);
+        }
+        i = i0 + 4 * nv;
+    }
+    for (long long j = i + threadIdx.x; j < i1; j += 512) {
+        const double x = (double)t.g[j];
+        s0 = fma(x, x, s0);
+        if (j + 256 < i1) { const double y = (double)t.g[j + 256]; s1 = fma(y, y, s1); }
+    }
+    double s = s0 + s1;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[c] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// ONE workgroup of T threads: S = partials[0] + ... + partials[n - 1] (+ *extra) in a fixed order, out[0] = the norm, out[1] = torch's
+// clip coefficient min(1, max_norm / (norm + 1e-6)).  A NaN sum gives a NaN coefficient (fmin would swallow it), an infinite one gives 0.
+template <int T>
+__global__ __launch_bounds__(T) void grad_coef_kernel(const double* partials, long long n, const double* extra, float max_norm, float* out) {
+    __shared__ double red[T];
+    double s = 0.0;
+    for (long long i = threadIdx.x; i < n; i += T) s += partials[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = T >> 1; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double S = red[0] + (extra ? *extra : 0.0);
+        const double norm = sqrt(S);
+        const double r = (double)max_norm / (norm + 1e-6);
+        out[0] = (float)norm;
+        out[1] = S != S ? (float)S : (float)(r < 1.0 ? r : 1.0);
+    }
+}
+
+// g <- g * *grad_scale.  The coefficient is read first: a workgroup that finds exactly 1 (nothing to clip) touches neither table nor gradient.
+__global__ __launch_bounds__(256) void grad_scale_kernel(const mi_adam_params a) {
+    const float g1 = *a.grad_scale;
+    if (g1 == 1.0f) return;
+    unsigned gb = __float_as_uint(g1);
+    MI_OPAQUE(gb);                                  // into a VGPR: no packed fp32 multiply with a scalar operand (csrc/Makefile)
+    const float gs = __uint_as_float(gb);
+    const int c = blockIdx.x;
+    const mi_adam_tensor t = a.tensors[a.chunk_tensor[c]];
+    float* const g = const_cast<float*>(t.g);
+    const long long i0 = (long long)a.chunk_off[c] * a.chunk;
+    const long long i1 = i0 + a.chunk < t.n ? i0 + a.chunk : t.n;
+    for (long long i = i0 + threadIdx.x; i < i1; i += 256) g[i] = g[i] * gs;
+}
+
+bool adam_tables_ok(const mi_adam_params* a, const char* who) {
+    if (!a || a->nchunks <= 0 || a->chunk <= 0 || !a->tensors || !a->chunk_tensor || !a->chunk_off) {
+        mi_set_error("%s: empty / missing tables", who);
+        return false;
+    }
+    return true;
+}
+
 bool ema_tables_ok(const mi_ema_params* a, const char* who) {
     if (!a || a->nchunks <= 0 || a->chunk <= 0 || !a->tensors || !a->chunk_tensor || !a->chunk_off) {
         mi_set_error("%s: empty / missing tables", who);
@@ -116,4 +199,29 @@ extern "C" int mi_ema_swap(const mi_ema_params* a, void* stream) {
     if (!ema_tables_ok(a, "mi_ema_swap")) return MI_ERR_INVALID;
     hipLaunchKernelGGL(ema_swap_kernel, dim3(a->nchunks), dim3(256), 0, (hipStream_t)stream, *a);
     return mi_check_launch("ema_swap_kernel");
+}
+
+extern "C" int mi_grad_sumsq(const mi_adam_params* a, double* partials, void* stream) {
+    if (!adam_tables_ok(a, "mi_grad_sumsq")) return MI_ERR_INVALID;
+    if (!partials) { mi_set_error("mi_grad_sumsq: NULL partials"); return MI_ERR_INVALID; }
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(a->nchunks), dim3(256), 0, (hipStream_t)stream, *a, partials);
+    return mi_check_launch("grad_sumsq_kernel");
+}
+
+extern "C" int mi_grad_clip_coef(const double* partials, long long n, const double* extra, float max_norm, float* out, void* stream) {
+    if (!out) { mi_set_error("mi_grad_clip_coef: NULL out"); return MI_ERR_INVALID; }
+    if (n < 0) { mi_set_error("mi_grad_clip_coef: n must not be negative"); return MI_ERR_INVALID; }
+    if (n > 0 && !partials) { mi_set_error("mi_grad_clip_coef: NULL partials"); return MI_ERR_INVALID; }
+    if (n == 0 && !extra) { mi_set_error("mi_grad_clip_coef: nothing to sum (n == 0 and no extra)"); return MI_ERR_INVALID; }
+    if (!(max_norm >= 0.0f)) { mi_set_error("mi_grad_clip_coef: max_norm must not be negative or NaN"); return MI_ERR_INVALID; }
+    if (n > 4096) hipLaunchKernelGGL(grad_coef_kernel<1024>, dim3(1), dim3(1024), 0, (hipStream_t)stream, partials, n, extra, max_norm, out);
+    else hipLaunchKernelGGL(grad_coef_kernel<256>, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, extra, max_norm, out);
+    return mi_check_launch("grad_coef_kernel");
+}
+
+extern "C" int mi_grad_scale(const mi_adam_params* a, void* stream) {
+    if (!adam_tables_ok(a, "mi_grad_scale")) return MI_ERR_INVALID;
+    if (!a->grad_scale) { mi_set_error("mi_grad_scale: NULL grad_scale"); return MI_ERR_INVALID; }
+    hipLaunchKernelGGL(grad_scale_kernel, dim3(a->nchunks), dim3(256), 0, (hipStream_t)stream, *a);
+    return mi_check_launch("grad_scale_kernel");
 }

@@ -6,7 +6,11 @@ optimiser loads into the other.  Parameters that are not fp32 / not on the GPU /
 
 ``EMA`` keeps an exponential moving average of the parameters: one fp32 shadow per parameter, updated by ``mi_ema_update`` -- or,
 attached to an ``Adam``, inside that optimiser's launch (``mi_adam_ema_step``) -- and exchanged with the live weights by ``mi_ema_swap`` for
-validation and sampling (``average_parameters()``)."""
+validation and sampling (``average_parameters()``).
+
+``clip_grad_norm_`` is torch.nn.utils.clip_grad_norm_ for the 2-norm on the device: ``mi_grad_sumsq`` -> ``mi_grad_clip_coef`` ->
+``mi_grad_scale``, the norm accumulated in fp64, no host synchronisation.  ``Adam(max_grad_norm=...)`` is the deferred form: no scaling pass,
+the Adam launch reads the coefficient through ``grad_scale`` and the gradients are never rewritten."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,18 +23,110 @@ from . import _lib as L
 
 CHUNK = 4096           # elements per launched workgroup
 
+_clip_tables = {}      # clip_grad_norm_: rows -> uploaded table (bounded: cleared when full)
+_partials_buf = {}     # device -> fp64 buffer of per-chunk sums of squares, grown on demand
+
+
+def _partials(dev, n: int):
+    buf = _partials_buf.get(dev)
+    if buf is None or buf.numel() < n:
+        buf = _partials_buf[dev] = torch.empty(max(n, 1024), dtype=torch.float64, device=dev)
+    return buf
+
+
+def _grad_block(tb, grad_scale=None) -> "L.MiAdamParams":
+    """mi_adam_params over an uploaded (tensor table, chunk tensor, chunk offset, chunk count): what the mi_grad_* entries read"""
+    a = L.MiAdamParams()
+    a.tensors, a.chunk_tensor, a.chunk_off, a.nchunks, a.chunk = tb[0].data_ptr(), tb[1].data_ptr(), tb[2].data_ptr(), tb[3], CHUNK
+    a.grad_scale = grad_scale
+    return a
+
+
+def _squares(g):
+    """sum of squares of a gradient the kernels do not take, as a 0-dim double on its own device"""
+    x = g.coalesce().values() if g.is_sparse else g
+    return x.detach().to(torch.float64).pow(2).sum()
+
+
+def _grad_eligible(g) -> bool:
+    return g.layout == torch.strided and g.dtype == torch.float32 and g.is_contiguous() and g.numel() > 0 and (g.is_cuda or L.backend() == "hipemu")
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ with the 2-norm taken and applied by three launches for all eligible gradients (dense, fp32,
+    contiguous, on the GPU): ``mi_grad_sumsq`` (per-chunk sums of squares in fp64), ``mi_grad_clip_coef`` (the norm and torch's coefficient
+    ``min(1, max_norm / (norm + 1e-6))``) and ``mi_grad_scale`` (in place; exits without touching memory when nothing is clipped).  The
+    other gradients enter the same norm through double torch ops and are scaled by the same coefficient.  Returns the total norm before
+    clipping, a 0-dim fp32 tensor on the gradients' device (a fresh one per call); the host is not synchronised unless
+    ``error_if_nonfinite`` is set, which reads the norm and raises torch's ``RuntimeError`` before anything is scaled.
+
+    The whole call is handed to ``torch.nn.utils.clip_grad_norm_`` when ``norm_type != 2``, when the eligible gradients sit on more than
+    one device, and when no gradient is eligible.  No gradients at all returns ``torch.tensor(0.)`` like torch."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    parameters = list(parameters)
+    max_norm, norm_type = float(max_norm), float(norm_type)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.)
+    fast = [g for g in grads if _grad_eligible(g)]
+    if norm_type != 2.0 or not fast or len({g.device for g in fast}) > 1:
+        return torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type, error_if_nonfinite, foreach)
+    if not max_norm >= 0.0:
+        raise ValueError(f"clip_grad_norm_: max_norm must not be negative or NaN, got {max_norm}")
+    taken = {id(g) for g in fast}
+    slow = [g for g in grads if id(g) not in taken]
+    dev, lib, stream = fast[0].device, L.lib(), L.current_stream()
+    # (zero_grad(set_to_none=True) re-allocates the gradients: the caching allocator usually hands the same blocks back, and the table holds)
+    rows = tuple((0, g.data_ptr(), 0, 0, g.numel()) for g in fast)
+    tb = _clip_tables.get((dev, rows))
+    if tb is None:
+        if len(_clip_tables) >= 8:
+            _clip_tables.clear()
+        tb = _clip_tables[(dev, rows)] = _upload(rows, dev)
+    partials = _partials(dev, tb[3])
+    L.check(lib.mi_grad_sumsq(C.byref(_grad_block(tb)), partials.data_ptr(), stream), "mi_grad_sumsq")
+    extra = None
+    if slow:
+        extra = torch.zeros((), dtype=torch.float64, device=dev)
+        for g in slow:
+            extra += _squares(g).to(dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)       # fresh per call: a norm the caller keeps for logging is never overwritten
+    L.check(lib.mi_grad_clip_coef(partials.data_ptr(), tb[3], extra.data_ptr() if extra is not None else None, max_norm, out.data_ptr(), stream),
+            "mi_grad_clip_coef")
+    if error_if_nonfinite and not bool(torch.isfinite(out[0])):
+        raise RuntimeError(f"The total norm of order {norm_type} for gradients from `parameters` is non-finite, so it cannot be clipped. To disable "
+                           "this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
+    L.check(lib.mi_grad_scale(C.byref(_grad_block(tb, out.data_ptr() + 4)), stream), "mi_grad_scale")
+    for g in fast:                                          # written through raw pointers: tell autograd / every version-keyed cache
+        torch.autograd.graph.increment_version(g)
+    for g in slow:
+        g.mul_(out[1].to(g.device))
+    return out[0]
+
 
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0., amsgrad: bool = False,
-                 maximize: bool = False, capturable: bool = False):
+                 maximize: bool = False, capturable: bool = False, *, max_grad_norm=None):
+        """``max_grad_norm`` (keyword-only, not in torch): clip the global 2-norm of the gradients of ALL groups at this value inside
+        ``step()`` -- ``mi_grad_sumsq`` per launch table, one ``mi_grad_clip_coef``, and the Adam launches read the coefficient through
+        ``grad_scale``.  The gradients themselves are NOT modified (the one visible difference from clipping in place with
+        ``clip_grad_norm_``); ``optimizer.grad_norm`` is the norm before clipping of the last step, a fresh 0-dim device tensor per step
+        (None before the first).  An attribute of the optimiser, not part of ``param_groups`` / ``state_dict()``.  None: exactly the
+        launches of an optimiser without it."""
         if amsgrad or maximize or capturable:
             raise NotImplementedError("minimagen_amd.optim.Adam implements torch.optim.Adam's default update only (no amsgrad / maximize / capturable)")
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or not 0.0 <= weight_decay:
             raise ValueError("invalid Adam hyper-parameters")
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"invalid max_grad_norm: {max_grad_norm}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._tables = {}
         self._count = {}          # parameter -> step count as a Python int (mirrored into the state's host ``step`` tensor at every step)
         self._ema = None          # an EMA whose shadow update rides in this optimiser's launch (EMA.attach)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm = None     # with max_grad_norm: the last step's total gradient norm before clipping (0-dim device tensor)
 
     def _state_of(self, p):
         st = self.state[p]
@@ -80,6 +176,40 @@ class Adam(torch.optim.Optimizer):
         self._tables[gi] = tb
         return tb
 
+    def _clip_coef(self, work):
+        """the deferred clip: the global 2-norm over every gradient this step takes (all groups, kernel and slow path) -> ``grad_norm``;
+        returns the clip coefficient as a 0-dim fp32 tensor, on the device of the kernel-path gradients"""
+        tables = [(ps, tb) for _, tabs, _ in work for _, _, ps, tb in tabs]
+        slow = [p.grad for _, _, sl in work for p in sl]
+        if not tables:                                      # nothing the kernels take: torch ops, the same formulas in double
+            if not slow:
+                self.grad_norm = torch.tensor(0.)
+                return None
+            S = torch.stack([_squares(g).to(slow[0].device) for g in slow]).sum()
+            norm = S.sqrt()
+            self.grad_norm = norm.float()
+            return (self.max_grad_norm / (norm + 1e-6)).clamp(max=1.0).float()
+        dev = tables[0][0][0].device
+        if any(ps[0].device != dev for ps, _ in tables):
+            raise NotImplementedError("minimagen_amd.optim.Adam: max_grad_norm needs the kernel-path parameters on one device")
+        lib, stream = L.lib(), L.current_stream()
+        n = sum(tb[4] for _, tb in tables)
+        partials = _partials(dev, n)
+        at = 0
+        for _, tb in tables:                                # one launch per table, each into its own slice
+            L.check(lib.mi_grad_sumsq(C.byref(_grad_block(tb[1:])), partials.data_ptr() + 8 * at, stream), "mi_grad_sumsq")
+            at += tb[4]
+        extra = None
+        if slow:
+            extra = torch.zeros((), dtype=torch.float64, device=dev)
+            for g in slow:
+                extra += _squares(g).to(dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        L.check(lib.mi_grad_clip_coef(partials.data_ptr(), n, extra.data_ptr() if extra is not None else None, self.max_grad_norm, out.data_ptr(),
+                                      stream), "mi_grad_clip_coef")
+        self.grad_norm = out[0]
+        return out[1]
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -90,8 +220,8 @@ class Adam(torch.optim.Optimizer):
         ema = self._ema
         ema_w = ema.advance() if ema is not None else None        # None: no shadow update is due at this step -> exactly the launches of an optimiser with nothing attached
         fused = []
+        work = []                                           # per group: (group, [(slot, step count, parameters, table)], slow-path parameters)
         for gi, group in enumerate(self.param_groups):
-            b1, b2 = group["betas"]
             fast, slow = [], []
             for p in group["params"]:
                 if p.grad is None:
@@ -110,13 +240,18 @@ class Adam(torch.optim.Optimizer):
             for p in fast:
                 by_step.setdefault(float(self._count[p]), []).append(p)
             # (table slots are keyed by group and position among the distinct counts, not by the count itself: nothing accumulates per step)
-            for slot, (t, ps) in enumerate(by_step.items()):
-                _, tens, ct, co, nchunks = self._table((gi, slot), ps)
+            work.append((group, [(slot, t, ps, self._table((gi, slot), ps)) for slot, (t, ps) in enumerate(by_step.items())], slow))
+        coef = self._clip_coef(work) if self.max_grad_norm is not None else None
+        for gi, (group, tables, slow) in enumerate(work):
+            b1, b2 = group["betas"]
+            for slot, t, ps, (_, tens, ct, co, nchunks) in tables:
                 a = L.MiAdamParams()
                 a.tensors, a.chunk_tensor, a.chunk_off, a.nchunks, a.chunk = tens.data_ptr(), ct.data_ptr(), co.data_ptr(), nchunks, CHUNK
                 a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = group["lr"], b1, b2, group["eps"], group["weight_decay"]
                 a.bias_correction1, a.bias_correction2 = 1.0 - b1 ** t, 1.0 - b2 ** t
                 a.one_minus_beta1, a.one_minus_beta2 = 1.0 - b1, 1.0 - b2
+                if coef is not None:
+                    a.grad_scale = coef.data_ptr()          # (on this table's device: _clip_coef checked; kept alive by grad_norm's storage)
                 rows = [ema._shadow_of.get(p) for p in ps] if ema_w is not None else None
                 if rows is not None and all(e is not None and e.device == p.device for e, p in zip(rows, ps)):
                     e = ema._params(("adam", gi, slot), ps, ema_w)
@@ -128,7 +263,8 @@ class Adam(torch.optim.Optimizer):
                     torch.autograd.graph.increment_version(p)
             for p in slow:                                  # torch's single-tensor update, same formulas
                 st = self.state[p]
-                g = p.grad if group["weight_decay"] == 0 else p.grad.add(p, alpha=group["weight_decay"])
+                g = p.grad if coef is None else p.grad * coef.to(p.grad.device)
+                g = g if group["weight_decay"] == 0 else g.add(p, alpha=group["weight_decay"])
                 t = float(self._count[p])
                 st["exp_avg"].lerp_(g, 1 - b1)
                 st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)

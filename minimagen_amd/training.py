@@ -152,7 +152,7 @@ def _save_ema(training_dir, imagen, n_unets, ema):
 
 
 def MinimagenTrain(timestamp, args, unets, imagen, train_dataloader, valid_dataloader, training_dir, optimizer, timeout=60, fail_fast=False, *,
-                   ema=None):
+                   ema=None, grad_clip="torch"):
     """training.py:344-478.  Per batch: for every U-Net of the cascade ``imagen(images, text_embeds, text_masks, unet_number)`` ->
     ``backward`` -> gradient-norm clip at 50 over ALL parameters; optimiser step every ACCUM_ITER batches (and at the last batch); every
     CHCKPT_NUM batches: rolling checkpoints in ``tmp/``, running / batch losses, a validation pass, best-so-far state dicts in ``state_dicts/``.
@@ -164,7 +164,15 @@ def MinimagenTrain(timestamp, args, unets, imagen, train_dataloader, valid_datal
     also writes the averaged U-Nets to ``ema_tmp/unet_<i>_tmp.pth`` and the EMA's state to ``ema_tmp/ema_state.pth``, validates a second time
     on the averaged weights (``... (EMA)`` lines in the progress file) and keeps the best averaged U-Nets in
     ``ema_state_dicts/unet_<k>_state_<timestamp>.pth`` -- what ``generate.load_minimagen(directory, ema=True)`` reads.  ``tmp/`` and
-    ``state_dicts/`` hold what they hold without it."""
+    ``state_dicts/`` hold what they hold without it.
+
+    ``grad_clip`` (not in the reference): ``"torch"`` clips with ``torch.nn.utils.clip_grad_norm_`` as the reference does; ``"device"`` with
+    ``minimagen_amd.optim.clip_grad_norm_`` -- the same place, the same meaning: in place, at 50, after every U-Net's backward,
+    over all parameters."""
+    if grad_clip not in ("torch", "device"):
+        raise ValueError(f'grad_clip must be "torch" or "device", got {grad_clip!r}')
+    if grad_clip == "device":
+        from .optim import clip_grad_norm_ as _device_clip
     n = len(unets)
     best = [torch.tensor(9999999.) for _ in range(n)]
     best_ema = [torch.tensor(9999999.) for _ in range(n)]
@@ -237,7 +245,10 @@ def MinimagenTrain(timestamp, args, unets, imagen, train_dataloader, valid_datal
                         losses[k] = loss.detach()
                         running[k] = running[k] + loss.detach()
                         loss.backward()
-                        torch.nn.utils.clip_grad_norm_(params, 50)
+                        if grad_clip == "device":
+                            _device_clip(params, 50)
+                        else:
+                            torch.nn.utils.clip_grad_norm_(params, 50)
                     if args.ACCUM_ITER == 1 or (batch_num % args.ACCUM_ITER == 0) or (batch_num + 1 == len(train_dataloader)):
                         optimizer.step()
                         if ema is not None and not ema_fused:
