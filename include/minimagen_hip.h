@@ -754,6 +754,66 @@ int mi_ema_update(const mi_ema_params* p, void* stream);
 int mi_adam_ema_step(const mi_adam_params* a, const mi_ema_params* e, void* stream);
 int mi_ema_swap(const mi_ema_params* p, void* stream);
 
+/* ---- prediction objectives of the training path: the front and the loss of Imagen._p_losses ---------------------------------
+ * For a U-Net that predicts the noise eps, x0 or v = sqrt(abar) eps - sqrt(1 - abar) x0, with a per-sample loss weight looked up by timestep
+ * on the device (min-SNR-gamma).  Struct indices 31 and 32 of mi_struct_size (30 stays unassigned: mi_struct_size(30) is -1); added within ABI 12
+ * (no existing struct or entry changed).
+ *
+ * mi_diffuse_fwd, ONE launch over (chunks of MI_OBJECTIVE_CHUNK elements, B), per image b with t = times[b], a = table[2 t], s = table[2 t + 1]
+ * (the fp32 values of sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod):
+ *     x0 = normalize ? x * 2 - 1 : x            x_t = a * x0 + s * noise
+ *     target = a * noise - s * x0 (MI_TARGET_V) | x0 (MI_TARGET_X_START) | not written (MI_TARGET_NONE: target may be NULL -- the noise
+ *     objective, whose target is `noise` itself, and the low-resolution conditioning image)
+ * every product and sum rounded on its own, in this order: the bits of the torch expressions.  16-byte accesses when n % 4 == 0 and the
+ * pointers are 16-byte aligned, element by element otherwise.  A timestep outside [0, T) reads nothing: that image's outputs are NaN.
+ * MI_ERR_INVALID: B, n or T not positive, B > 65535, n > 2^30, a NULL pointer, an unknown target_kind, a target asked for without `target`. */
+#define MI_OBJECTIVE_CHUNK 4096
+#define MI_TARGET_NONE 0
+#define MI_TARGET_V 1
+#define MI_TARGET_X_START 2
+typedef struct {
+    int B, n;                       /* images, elements per image */
+    int T;                          /* rows of `table` */
+    int normalize, target_kind;
+    const float* x;                 /* [B][n] */
+    const float* noise;             /* [B][n] */
+    const long long* times;         /* [B], device */
+    const float* table;             /* [T][2], device */
+    float* x_t;                     /* [B][n] */
+    float* target;                  /* [B][n] or NULL */
+    long long reserved[2];
+} mi_diffuse_params;
+int mi_diffuse_fwd(const mi_diffuse_params* p, void* stream);
+/* chunks per image of the two entries around this line: ceil(n / MI_OBJECTIVE_CHUNK) */
+int mi_objective_chunks(int n);
+
+/* loss[0] = (1 / (B n)) sum_b w[times[b]] sum_i l(pred[b][i] - target[b][i]), l = |d| (MI_LOSS_L1), d^2 (MI_LOSS_L2) or smooth-l1 with beta = 1
+ * (MI_LOSS_SMOOTH_L1: d^2 / 2 below |d| = 1, |d| - 1/2 from there).  The difference is taken in fp32, l and every sum in fp64; partials[b * nc + c]
+ * (nc = mi_objective_chunks(n)) depends on chunk c of image b alone and a one-workgroup second launch adds the partials in a fixed order: no
+ * atomics, two runs give the same bits.  The loss is written as one fp32 on the device; nothing comes back to the host.  weights: fp32 [T] on
+ * the device, read through times (a timestep outside [0, T) makes the loss NaN), or NULL for w = 1 (times is then not read).  grad != NULL: the
+ * same pass writes g = w l'(d) / (B n) (formed in fp64, rounded once; l' of |d| is sign(d), 0 at 0).  NaN / inf in pred reach the loss.
+ * MI_ERR_INVALID: B or n not positive, B > 65535, n > 2^30, NULL pred / target / partials / loss, an unknown loss_type, weights without times / T. */
+#define MI_LOSS_L1 0
+#define MI_LOSS_L2 1
+#define MI_LOSS_SMOOTH_L1 2
+typedef struct {
+    int B, n;
+    int loss_type;
+    int T;                          /* entries of `weights` */
+    const float* pred;              /* [B][n] */
+    const float* target;            /* [B][n] */
+    const long long* times;         /* [B], device (with weights) */
+    const float* weights;           /* [T], device, or NULL */
+    double* partials;               /* [B * mi_objective_chunks(n)], device scratch */
+    float* loss;                    /* [1], device */
+    float* grad;                    /* [B][n] or NULL */
+    long long reserved[2];
+} mi_objective_loss_params;
+int mi_objective_loss_fwd(const mi_objective_loss_params* p, void* stream);
+/* dpred[i] = g[i] * *grad_out for i < count, grad_out read from device memory (the backward of mi_objective_loss_fwd: g is its `grad`) */
+int mi_objective_loss_bwd(const float* g, const float* grad_out, float* dpred, long long count, void* stream);
+
 /* ---- HIP graphs: capture a sequence of the calls above once, replay it per timestep ------- */
 int mi_graph_begin(void* stream);
 int mi_graph_end(void* stream, void** graph_exec);

@@ -11,6 +11,7 @@ from torch import nn
 
 from . import _lib as L
 from . import sampler as S
+from . import train_ops
 from .Unet import Unet
 from .diffusion_model import GaussianDiffusion
 from .helpers import (cast_tuple, default, eval_decorator, exists, module_device, normalize_neg_one_to_one, resize_image_to)
@@ -51,8 +52,15 @@ class Imagen(nn.Module):
             lowres_sample_noise_level: float = 0.2,
             auto_normalize_img: bool = True,
             dynamic_thresholding_percentile: float = 0.9,
-            only_train_unet_number: int = None
+            only_train_unet_number: int = None,
+            pred_objectives: Union[str, List[str], Tuple[str, ...]] = 'noise',
+            min_snr_loss_weight: Union[bool, List[bool], Tuple[bool, ...]] = False,
+            min_snr_gamma: Union[float, List[float], Tuple[float, ...]] = 5.
     ):
+        """Not in the reference (keyword-only, one value or one per U-Net): ``pred_objectives`` = what each U-Net predicts and
+        is trained on -- 'noise' (the reference's), 'x_start' or 'v' (Salimans & Ho 2022: sqrt(abar) eps - sqrt(1 - abar) x0);
+        ``min_snr_loss_weight`` with ``min_snr_gamma`` > 0: the min-SNR-gamma loss weight per timestep (Hang et al. 2023;
+        GaussianDiffusion.loss_weight_table).  Bad values raise ValueError.  The defaults are the reference's training and sampling."""
         super().__init__()
         if loss_type not in ('l1', 'l2', 'huber'):
             raise NotImplementedError()
@@ -60,6 +68,21 @@ class Imagen(nn.Module):
         self.channels = channels
         unets = cast_tuple(unets)
         num_unets = len(unets)
+
+        def per_unet(val, name, ok, what):
+            vals = tuple(val) if isinstance(val, (list, tuple)) else (val,) * num_unets      # (the parameter JSON turns tuples into lists)
+            if len(vals) != num_unets:
+                raise ValueError(f"{name} needs one value per U-Net ({num_unets}), got {len(vals)}")
+            for v in vals:
+                if not ok(v):
+                    raise ValueError(f"{name} must be {what}, got {v!r}")
+            return vals
+        self.pred_objectives = per_unet(pred_objectives, "pred_objectives", lambda v: isinstance(v, str) and v in GaussianDiffusion.OBJECTIVES,
+                                        f"one of {GaussianDiffusion.OBJECTIVES}")
+        self.min_snr_loss_weight = per_unet(min_snr_loss_weight, "min_snr_loss_weight", lambda v: isinstance(v, bool), "a bool")
+        self.min_snr_gamma = tuple(float(v) for v in per_unet(
+            min_snr_gamma, "min_snr_gamma", lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and v > 0. and v == v, "a positive number"))
+        self._loss_weights = {}                  # (U-Net index, device) -> the fp32 weight table of that U-Net's min-SNR setting, where the loss reads it
         self.noise_schedulers = nn.ModuleList([GaussianDiffusion(timesteps=t) for t in cast_tuple(timesteps, num_unets)])
         # built from the RAW argument like Imagen.py:78 (so only an int works, as in the reference)
         self.lowres_noise_schedule = GaussianDiffusion(timesteps=timesteps)
@@ -113,9 +136,28 @@ class Imagen(nn.Module):
         return self.unets[unet_number - 1]
 
     def _p_losses(self, unet: Unet, x_start, times, *, noise_scheduler: GaussianDiffusion, lowres_cond_img=None, lowres_aug_times=None,
-                  text_embeds=None, text_mask=None, noise=None):
-        """Imagen.py:512-573: corrupt x_0 with q_sample, predict the noise, loss against the true noise"""
+                  text_embeds=None, text_mask=None, noise=None, unet_index: int = None):
+        """Imagen.py:512-573: corrupt x_0 with q_sample, predict the noise, loss against the true noise.  A U-Net with another objective or with
+        the min-SNR weight (``unet_index``: which one, default the one _get_unet handed out last) goes through train_ops.diffuse /
+        train_ops.objective_loss: same draws in the same order, the target and the weighted loss of DESIGN.md section 20."""
+        k = default(unet_index, max(self.unet_being_trained_index, 0))
+        objective, weighted = self.pred_objectives[k], self.min_snr_loss_weight[k]
         noise = default(noise, lambda: torch.randn_like(x_start))
+        if objective != 'noise' or weighted:
+            x_noisy, target = train_ops.diffuse(x_start, noise, times, noise_scheduler, normalize=self.auto_normalize_img, target=objective)
+            lowres_noisy = None
+            if exists(lowres_cond_img):
+                lowres_aug_times = default(lowres_aug_times, times)
+                lowres_noisy, _ = train_ops.diffuse(lowres_cond_img, torch.randn_like(lowres_cond_img), lowres_aug_times, self.lowres_noise_schedule,
+                                                    normalize=self.auto_normalize_img, target=None)
+            pred = unet.forward(x_noisy, times, text_embeds=text_embeds, text_mask=text_mask, lowres_noise_times=lowres_aug_times,
+                                lowres_cond_img=lowres_noisy, cond_drop_prob=self.cond_drop_prob)
+            weights = None
+            if weighted:
+                weights = self._loss_weights.get((k, pred.device))
+                if weights is None:
+                    weights = self._loss_weights[(k, pred.device)] = noise_scheduler.loss_weight_table(objective, self.min_snr_gamma[k]).to(pred.device)
+            return train_ops.objective_loss(pred, target, times, weights, self.loss_type)
         norm = normalize_neg_one_to_one if self.auto_normalize_img else (lambda v: v)
         x_start = norm(x_start)
         x_noisy = noise_scheduler.q_sample(x_start=x_start, t=times, noise=noise)
@@ -158,7 +200,7 @@ class Imagen(nn.Module):
             lowres_aug_times = self.lowres_noise_schedule._sample_random_times(1, device=images.device).expand(b)
         images = resize_image_to(images, target)
         return self._p_losses(unet, images, times, text_embeds=text_embeds, text_mask=text_masks, noise_scheduler=noise_scheduler,
-                              lowres_cond_img=lowres_cond_img, lowres_aug_times=lowres_aug_times)
+                              lowres_cond_img=lowres_cond_img, lowres_aug_times=lowres_aug_times, unet_index=k)
 
     # ------------------------------------------------------------------ sampling
     # ------------------------------------------------------------------ sampling (the loop itself: minimagen_amd/sampler.py)
@@ -300,7 +342,11 @@ class Imagen(nn.Module):
         ``start_at_stage`` = s >= 1 skips the stages below s and stands in for the output of stage s - 1 (run only the super-resolution
         stage on an image of the caller's); ``stop_at_stage`` = s runs the stages below s and returns that stage's image.  The noise is
         keyed by the stage INDEX, so a cascade cut in two this way gives the bits of the whole.  A call with none of these goes through
-        exactly the states, tables, graphs and kernels it went through before they existed."""
+        exactly the states, tables, graphs and kernels it went through before they existed.
+
+        A stage whose U-Net was built with ``pred_objectives`` 'v' or 'x_start' samples from a coefficient table whose columns 0 and 1 turn
+        that prediction into x0 (GaussianDiffusion.sampler_coef_table), for every setting above; nothing else differs, and a 'noise' stage is
+        untouched."""
         solvers = self._parse_solver(sample_steps, sampler, sampler_eta)
         if exists(text_embeds) or exists(texts):
             first_stage, end_stage, inpaint, start_image = self._parse_inpaint(text_embeds.shape[0] if exists(text_embeds) else len(texts), inpaint_images,
@@ -384,6 +430,9 @@ class Imagen(nn.Module):
         precision = _precision if _precision is not None else os.environ.get("MINIMAGEN_PRECISION", "fp32")
         stages = list(enumerate(zip(self.unets, self.sample_channels, self.image_sizes, self.noise_schedulers)))[first_stage:end_stage]
         known = {} if inpaint is None else dict(inpaint=inpaint)        # (a call without known pixels passes nothing new down)
+        # ... and neither does a noise-predicting stage: only another objective names itself (it selects the stage's coefficient table)
+        extras = {stage: dict(known, **({} if self.pred_objectives[stage] == 'noise' else dict(objective=self.pred_objectives[stage])))
+                  for stage, _ in stages}
         # ---- pass 1, every stage on its own stream: what depends on the CAPTIONS only (text conditioning, the folded context rows, x_T, the
         # step tables) -- issued for all stages up front, so a later stage has it behind it when its low-resolution input arrives
         wss, begun = {}, {}
@@ -406,7 +455,7 @@ class Imagen(nn.Module):
                     ws.lowres_times.fill_(int(self.lowres_noise_schedule.num_timesteps * lowres_sample_noise_level))
                 if _noise is None:
                     begun[stage] = self._stage_begin(unet, (batch_size, self.channels, image_size, image_size), noise_scheduler=noise_scheduler,
-                                                     ws=ws, seed=_seed, sample0=_sample_offset, stage=stage, solver=solvers[stage], **known)
+                                                     ws=ws, seed=_seed, sample0=_sample_offset, stage=stage, solver=solvers[stage], **extras[stage])
         # ---- pass 2: the cascade
         img, prev_done = start_image, None
         for stage, (unet, channel, image_size, noise_scheduler) in stages:
@@ -420,7 +469,7 @@ class Imagen(nn.Module):
                     self._lowres_conditioning(unet, img, image_size, ws, lowres_sample_noise_level, _noise, _seed, _sample_offset, stage)
                 img = self._p_sample_loop(unet, (batch_size, self.channels, image_size, image_size), noise_scheduler=noise_scheduler,
                                           ws=ws, cond_scale=cond_scale, noise_fn=_noise, seed=_seed, sample0=_sample_offset,
-                                          stage=stage, use_graph=_use_graph, begun=begun.get(stage), solver=solvers[stage], **known)
+                                          stage=stage, use_graph=_use_graph, begun=begun.get(stage), solver=solvers[stage], **extras[stage])
                 if on_gpu:
                     prev_done = streams[stage].record_event()
         pack_tokens = [] if (_noise is not None or _revalidated) else [(unet.engine(), unet.engine().pack_begin()) for unet in self.unets]

@@ -221,6 +221,18 @@ class MiEmaParams(C.Structure):
                 ("w", C.c_float), ("reserved", C.c_int)]
 
 
+class MiDiffuseParams(C.Structure):
+    _fields_ = [("B", C.c_int), ("n", C.c_int), ("T", C.c_int), ("normalize", C.c_int), ("target_kind", C.c_int),
+                ("x", C.c_void_p), ("noise", C.c_void_p), ("times", C.c_void_p), ("table", C.c_void_p), ("x_t", C.c_void_p), ("target", C.c_void_p),
+                ("reserved", C.c_longlong * 2)]
+
+
+class MiObjectiveLossParams(C.Structure):
+    _fields_ = [("B", C.c_int), ("n", C.c_int), ("loss_type", C.c_int), ("T", C.c_int),
+                ("pred", C.c_void_p), ("target", C.c_void_p), ("times", C.c_void_p), ("weights", C.c_void_p), ("partials", C.c_void_p),
+                ("loss", C.c_void_p), ("grad", C.c_void_p), ("reserved", C.c_longlong * 2)]
+
+
 class MiPackConv3Desc(C.Structure):
     _fields_ = [("w", C.c_void_p), ("frag", C.c_void_p), ("generic", C.c_void_p), ("Cout", C.c_int), ("Cin", C.c_int), ("adjoint", C.c_int),
                 ("exp", C.c_int), ("cout_pad", C.c_int), ("reserved", C.c_int)]
@@ -230,7 +242,7 @@ _STRUCTS = {0: MiAct, 1: MiConvParams, 2: MiCrossEmbedParams, 3: MiLinear, 4: Mi
             6: MiAttnFoldParams, 7: MiCrossAttnParams, 8: MiCfgX0Params, 9: MiQuantileParams, 10: MiPosteriorParams,
             11: MiResizeParams, 12: MiSelfAttnParams, 13: MiChanFFParams, 14: MiFlashAttnParams, 15: MiTokensToNchwParams, 16: MiConvWgradParams, 17: MiBlockBwdParams, 18: MiCrossEmbedWgradParams, 19: MiFoldedAttnParams, 20: MiAdamTensor, 21: MiAdamParams, 22: MiPackConv3Desc,
             23: MiFlashAttnTrainParams, 24: MiSamplerExtParams, 25: MiInpaintParams, 26: MiInitDownParams, 27: MiAttnCondParams,
-            28: MiEmaTensor, 29: MiEmaParams}
+            28: MiEmaTensor, 29: MiEmaParams, 31: MiDiffuseParams, 32: MiObjectiveLossParams}
 
 _lib = None
 _backend = None
@@ -258,6 +270,12 @@ def _bind(lib):
     lib.mi_grad_clip_coef.argtypes = [vp, C.c_longlong, vp, f32, vp, vp]
     lib.mi_grad_scale.argtypes = [vp, vp]
     for name in ("mi_grad_sumsq", "mi_grad_clip_coef", "mi_grad_scale"):
+        getattr(lib, name).restype = i32
+    lib.mi_diffuse_fwd.argtypes = [vp, vp]
+    lib.mi_objective_loss_fwd.argtypes = [vp, vp]
+    lib.mi_objective_loss_bwd.argtypes = [vp, vp, vp, C.c_longlong, vp]
+    lib.mi_objective_chunks.argtypes = [i32]
+    for name in ("mi_diffuse_fwd", "mi_objective_loss_fwd", "mi_objective_loss_bwd", "mi_objective_chunks"):
         getattr(lib, name).restype = i32
     lib.mi_conv_prep_bytes.argtypes = [i32, i32, i32, i32, i32]
     lib.mi_conv_prep_bytes.restype = C.c_longlong

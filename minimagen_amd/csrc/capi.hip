@@ -56,6 +56,8 @@ extern "C" int mi_struct_size(int which) {
         case 27: return (int)sizeof(mi_attn_cond_params);
         case 28: return (int)sizeof(mi_ema_tensor);
         case 29: return (int)sizeof(mi_ema_params);
+        case 31: return (int)sizeof(mi_diffuse_params);             // (30 stays unassigned)
+        case 32: return (int)sizeof(mi_objective_loss_params);
     }
     return -1;
 }

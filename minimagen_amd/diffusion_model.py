@@ -71,10 +71,31 @@ class GaussianDiffusion(nn.Module):
         a = self._abar64()[-1]
         return float(torch.sqrt(a).to(torch.float32)), float(torch.sqrt(1. - a).to(torch.float32))
 
-    def sampler_coef_table(self, known: bool = False) -> torch.Tensor:
+    OBJECTIVES = ('noise', 'x_start', 'v')
+
+    @classmethod
+    def _check_objective(cls, objective):
+        if objective not in cls.OBJECTIVES:
+            raise ValueError(f'objective must be one of {cls.OBJECTIVES}, got {objective!r}')
+
+    @classmethod
+    def _objective_columns64(cls, a: torch.Tensor, objective: str):
+        """float64[S][2] or None ('noise': the table's own columns stay): columns 0 and 1 of a coefficient table whose rows sit at abar = ``a``,
+        so that x0 = c0 x_t - c1 pred for a U-Net that predicts ``objective`` (DESIGN.md section 20) -- 'v': (sqrt(abar), sqrt(1 - abar));
+        'x_start': exactly (0, -1), 0 x_t - (-1) pred being pred to the bit"""
+        cls._check_objective(objective)
+        if objective == 'noise':
+            return None
+        if objective == 'v':
+            return torch.stack((torch.sqrt(a), torch.sqrt(1. - a)), dim=1)
+        return torch.stack((torch.zeros_like(a), -torch.ones_like(a)), dim=1)
+
+    def sampler_coef_table(self, known: bool = False, objective: str = 'noise') -> torch.Tensor:
         """[T][8] table consumed by mi_cfg_x0_fwd / mi_posterior_fwd: per-timestep scalars gathered from the
         buffers above; column 4 is [t != 0] * exp(0.5 * posterior_log_variance_clipped) (Imagen.py:364-370).
-        ``known``: plus the inpainting columns 6 and 7 (fp64 from the betas, rounded once); without it they are zero."""
+        ``known``: plus the inpainting columns 6 and 7 (fp64 from the betas, rounded once); without it they are zero.
+        ``objective``: what the U-Net predicts -- 'v' / 'x_start' replace columns 0 and 1 (_objective_columns64: fp64 from the betas, rounded
+        once); 'noise' is the table as it was before the argument existed."""
         T = self.num_timesteps
         tab = torch.zeros(T, 8, dtype=torch.float32)
         cpu = lambda v: v.detach().to('cpu', torch.float32)
@@ -87,6 +108,9 @@ class GaussianDiffusion(nn.Module):
         tab[:, 4] = nonzero * (0.5 * cpu(self.posterior_log_variance_clipped)).exp()
         if known:
             tab[:, 6:8] = self._known_columns64(self._abar64()).to(torch.float32)
+        cols = self._objective_columns64(self._abar64(), objective)
+        if cols is not None:
+            tab[:, 0:2] = cols.to(torch.float32)
         return tab
 
     # ---- sampling in S <= T steps over a subsequence of the trained timesteps (not in the reference; DESIGN.md "Fewer sampling steps")
@@ -99,8 +123,9 @@ class GaussianDiffusion(nn.Module):
             raise ValueError(f'sample_steps must be in [2, {T}] for a schedule of {T} timesteps, got {steps}')
         return torch.tensor([(2 * k * (T - 1) + (S - 1)) // (2 * (S - 1)) for k in range(S)], dtype=torch.int64)
 
-    def _sampler_tables64(self, steps: int, sampler: str = 'ddpm', eta: float = None, known: bool = False):
+    def _sampler_tables64(self, steps: int, sampler: str = 'ddpm', eta: float = None, known: bool = False, objective: str = 'noise'):
         """sampler_tables before the rounding to fp32: (tau int64[S], abar float64[S], coef float64[S][8])"""
+        self._check_objective(objective)
         if sampler not in self.SAMPLERS:
             raise ValueError(f'sampler must be one of {self.SAMPLERS}, got {sampler!r}')
         if eta is not None and sampler != 'ddim':
@@ -141,17 +166,43 @@ class GaussianDiffusion(nn.Module):
                     tab[k, 5] = -m / (2. * r)
         if known:
             tab[:, 6:8] = self._known_columns64(a)
+        cols = self._objective_columns64(a, objective)
+        if cols is not None:
+            tab[:, 0:2] = cols
         return tau, a, tab
 
-    def sampler_tables(self, steps: int, sampler: str = 'ddpm', eta: float = None, known: bool = False):
+    def sampler_tables(self, steps: int, sampler: str = 'ddpm', eta: float = None, known: bool = False, objective: str = 'noise'):
         """(tau int64[S], coef float32[S][8]) for ``steps`` sampling steps over the trained timesteps tau: row k of ``coef`` is the step at
         timestep tau_k (the sampler walks k = S-1 .. 0).  With cN = column N (the naming of DESIGN.md section 14 and the C header): x0 = c0 x - c1 eps, then
         x' = c2 x0 + c3 x + c5 x0_prev + c4 z with the thresholded x0 of this and of the previous step.  'ddpm' is 'ddim' with eta = 1 (the reference's ancestral step when
         S = T); 'dpmpp_2m' is deterministic.  Everything in fp64 from the betas, rounded to fp32 once.  ``known``: plus c6 = sqrt(abar_{tau_{k-1}}) and
         c7 = sqrt(1 - abar_{tau_{k-1}}), the level an inpainting call re-imposes its known pixels at behind step k (row 0: exactly 1 and 0);
-        without it columns 6 and 7 are zero and the table is what it was before the flag existed."""
-        tau, _, tab = self._sampler_tables64(steps, sampler, eta, known)
+        without it columns 6 and 7 are zero and the table is what it was before the flag existed.  ``objective`` = 'v' / 'x_start': c0 and c1 turn
+        that prediction into x0 (sampler_coef_table); the solvers work on x0 and x only, so columns 2 .. 7 do not depend on it."""
+        tau, _, tab = self._sampler_tables64(steps, sampler, eta, known, objective)
         return tau, tab.to(torch.float32)
+
+    def loss_weight_table(self, objective: str, min_snr_gamma: float = None) -> torch.Tensor:
+        """float32[T], the per-timestep weight of the training loss of a U-Net that predicts ``objective``, in fp64 from the betas and rounded
+        once.  Min-SNR-gamma (Hang et al. 2023) with snr = abar / (1 - abar) and c = min(snr, gamma): 'noise' c / snr, 'x_start' c,
+        'v' c / (snr + 1).  Where snr is exactly 0 (abar underflows: T = 20) 'noise' takes its limit 1, the other two are 0.
+        ``min_snr_gamma`` None: all ones."""
+        self._check_objective(objective)
+        if min_snr_gamma is None:
+            return torch.ones(self.num_timesteps, dtype=torch.float32)
+        gamma = float(min_snr_gamma)
+        if not gamma > 0.:
+            raise ValueError(f'min_snr_gamma must be positive, got {min_snr_gamma!r}')
+        a = self._abar64()
+        snr = a / (1. - a)
+        c = snr.clamp(max=gamma)
+        if objective == 'noise':
+            w = torch.where(snr > 0., c / snr.clamp(min=torch.finfo(torch.float64).tiny), torch.ones_like(snr))
+        elif objective == 'x_start':
+            w = c
+        else:
+            w = c / (snr + 1.)
+        return w.to(torch.float32)
 
     # ---- the per-timestep helpers of the reference's public API (diffusion_model.py:89-162).  The sampling hot path has them fused
     # into the HIP sampler kernels (mi_lowres_augment, mi_cfg_x0_fwd, mi_posterior_fwd); these tensor forms serve callers of the class
@@ -175,3 +226,11 @@ class GaussianDiffusion(nn.Module):
     def predict_start_from_noise(self, x_t: torch.Tensor, t: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
         """x_0 = sqrt(1 / abar_t) x_t - sqrt(1 / abar_t - 1) eps (diffusion_model.py:149-162)"""
         return self._at(self.sqrt_recip_alphas_cumprod, t, x_t) * x_t - self._at(self.sqrt_recipm1_alphas_cumprod, t, x_t) * noise
+
+    def calculate_v(self, x_start: torch.Tensor, t: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+        """v = sqrt(abar_t) eps - sqrt(1 - abar_t) x_0 (Salimans & Ho 2022, appendix D)"""
+        return self._at(self.sqrt_alphas_cumprod, t, x_start) * noise - self._at(self.sqrt_one_minus_alphas_cumprod, t, x_start) * x_start
+
+    def predict_start_from_v(self, x_t: torch.Tensor, t: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """x_0 = sqrt(abar_t) x_t - sqrt(1 - abar_t) v"""
+        return self._at(self.sqrt_alphas_cumprod, t, x_t) * x_t - self._at(self.sqrt_one_minus_alphas_cumprod, t, x_t) * v

@@ -53,14 +53,17 @@ class StageState:
     (``hasattr`` is how callers ask for a solver extension / a grouped tail); ``t_map`` / ``group_err_host``, None until then, answer the same here.
     ``hw`` (pixels per channel plane) makes it the state of an INPAINTING call -- an entry of its own: the coefficient table with columns 6 and
     7, and the known-image / mask buffers every call copies into (so one captured graph serves every later call's images and masks);
-    ``ip`` (None otherwise) is the kernels' block over them, rebuilt by every stage_begin."""
+    ``ip`` (None otherwise) is the kernels' block over them, rebuilt by every stage_begin.  ``objective`` (what the stage's U-Net predicts: 'noise',
+    'x_start' or 'v') only chooses columns 0 and 1 of the coefficient table: no kernel, struct or launch knows about it."""
     __slots__ = ("coef", "tau", "t_map", "x0_prev", "ext", "t_state", "x0", "hist", "s_q", "v_q", "seed_dev", "graphs",
                  "group_sync", "group_err_host", "group_failed", "group_heal", "known", "mask", "ip", "known_noise")
 
-    def __init__(self, sched, B: int, n: int, dev, solver=None, hw: int = None):
+    def __init__(self, sched, B: int, n: int, dev, solver=None, hw: int = None, objective: str = 'noise'):
         self.tau = self.t_map = self.x0_prev = None     # the reference's loop has no step -> timestep map and no history
         self.known = self.mask = self.ip = self.known_noise = None
         known = {} if hw is None else dict(known=True)
+        if objective != 'noise':
+            known['objective'] = objective
         if hw is not None:
             self.known = torch.zeros(B, n, dtype=torch.float32, device=dev)
             self.mask = torch.zeros(B, hw, dtype=torch.uint8, device=dev)
@@ -91,11 +94,14 @@ class StageState:
         self.graphs.clear()
 
 
-def stage_state(ws, sched, B: int, n: int, solver=None, eng=None, max_states: int = 8, hw: int = None) -> StageState:
+def stage_state(ws, sched, B: int, n: int, solver=None, eng=None, max_states: int = 8, hw: int = None, objective: str = 'noise') -> StageState:
     """The workspace's state for this schedule / solver setting, keyed by T for the default call and (T, S, sampler, eta) otherwise; an
-    inpainting call (``hw``) has its own: that key plus an 'inpaint' marker, bounded together with the solver states."""
+    inpainting call (``hw``) has its own: that key plus an 'inpaint' marker, bounded together with the solver states.  An ``objective`` other
+    than 'noise' (another coefficient table) is appended to the key in the same way; the keys of a noise-predicting U-Net are what they were."""
     store = ws.sampler_state
     key = sched.num_timesteps if solver is None else (sched.num_timesteps,) + tuple(solver)
+    if objective != 'noise':
+        key = (key if isinstance(key, tuple) else (key,)) + (objective,)
     if hw is not None:
         key = (key if isinstance(key, tuple) else (key,)) + ("inpaint",)
     bounded = isinstance(key, tuple)
@@ -111,7 +117,7 @@ def stage_state(ws, sched, B: int, n: int, solver=None, eng=None, max_states: in
             if eng is not None:
                 eng.drop_step_tables(ws, old.t_state)
     if st is None:
-        st = store[key] = StageState(sched, B, n, ws.dev, solver, hw)
+        st = store[key] = StageState(sched, B, n, ws.dev, solver, hw, objective)
     return st
 
 
@@ -133,7 +139,7 @@ def known_begin(st: StageState, ws, shape, inpaint, *, sched, known_noise, seed:
 
 
 def stage_begin(unet, shape, *, noise_scheduler, ws, noise_fn=None, seed: int = 0, sample0: int = 0, stage: int = 0, solver=None, max_states: int = 8,
-                inpaint=None):
+                inpaint=None, objective: str = 'noise'):
     """Everything of a stage's loop that does not depend on the PREVIOUS stage's image: x_T (Imagen.py:400), the device-resident timestep, the
     per-step conditioning tables of all T steps -- and, for an inpainting call (``inpaint``: see known_begin), the stage's known image and mask
     and blend 0.  sample() issues it for every stage before the first stage's loop, so that a later stage's
@@ -142,7 +148,7 @@ def stage_begin(unet, shape, *, noise_scheduler, ws, noise_fn=None, seed: int = 
     lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
     B, n = shape[0], shape[1] * shape[2] * shape[3]
     T = noise_scheduler.num_timesteps if solver is None else solver[0]        # steps of the loop (one draw each, for every solver)
-    st = stage_state(ws, noise_scheduler, B, n, solver, eng, max_states, hw=None if inpaint is None else shape[2] * shape[3])
+    st = stage_state(ws, noise_scheduler, B, n, solver, eng, max_states, hw=None if inpaint is None else shape[2] * shape[3], objective=objective)
     noise_dev = known_noise = None
     if noise_fn is not None:
         ws.x.copy_(noise_fn(shape))                                          # Imagen.py:400
@@ -204,10 +210,12 @@ def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream):
 
 
 def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, noise_fn=None, seed: int = 0, sample0: int = 0,
-                  stage: int = 0, use_graph: bool = True, begun=None, solver=None, group_max: int = 8, max_states: int = 8, inpaint=None):
+                  stage: int = 0, use_graph: bool = True, begun=None, solver=None, group_max: int = 8, max_states: int = 8, inpaint=None,
+                  objective: str = 'noise'):
     """Imagen.py:373-420 + :329-370 + :261-326: T replays of [U-Net (both guidance halves) -> CFG combine + x0 -> dynamic-threshold quantile ->
     posterior draw -> t -= 1].  ``solver`` = (S, sampler, eta): S steps over a subsequence of the trained timesteps; the loop, the noise index and the
-    Philox stream count STEPS: the reference's loop with T = S but for the state's step -> timestep map and history buffer (``st.ext``)."""
+    Philox stream count STEPS: the reference's loop with T = S but for the state's step -> timestep map and history buffer (``st.ext``).
+    ``objective``: what the U-Net predicts; it selects the stage state (its coefficient table) and nothing else."""
     lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
     B, Cc, H, W = shape
     n = Cc * H * W
@@ -215,7 +223,7 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
     two = ws.B2 != ws.B
     if begun is None:
         begun = stage_begin(unet, shape, noise_scheduler=noise_scheduler, ws=ws, noise_fn=noise_fn, seed=seed, sample0=sample0, stage=stage, solver=solver, max_states=max_states,
-                            inpaint=inpaint)
+                            inpaint=inpaint, objective=objective)
     st, noise_dev = begun
     k_lo, k_hi, w = quantile_rank(n, im.dynamic_thresholding_percentile)
     # the whole tail in one launch: of one workgroup per image (n <= MI_SAMPLER_SMALL_N), or of <= group_max (0: never) cooperating workgroups -- but

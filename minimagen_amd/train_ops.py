@@ -798,3 +798,103 @@ def block_supported(block, x: torch.Tensor) -> bool:
     gnm = block.groupnorm
     groups = gnm.num_groups if isinstance(gnm, torch.nn.GroupNorm) else 0
     return conv_shape_supported(block.project.in_channels, block.project.out_channels, x.shape[-1], groups)
+
+
+# ---- the front and the loss of a training step for the prediction objectives (csrc/objective.hip)
+_TARGET_KINDS = {None: 0, 'noise': 0, 'v': 1, 'x_start': 2}           # MI_TARGET_*: the noise objective's target is the caller's noise tensor
+_LOSS_KINDS = {'l1': 0, 'l2': 1, 'huber': 2}                            # MI_LOSS_*
+_LOSS_FNS = {'l1': F.l1_loss, 'l2': F.mse_loss, 'huber': F.smooth_l1_loss}
+
+
+def objective_active(x: torch.Tensor) -> bool:
+    """mi_diffuse_fwd / mi_objective_loss_fwd run for fp32 GPU tensors (and for host tensors when a test forces the emulator), with or without
+    autograd: the no-grad evaluation of the loss takes them too"""
+    return ENABLED and x.dtype == torch.float32 and (x.is_cuda or FORCE)
+
+
+def _diffuse_table(sched, dev) -> torch.Tensor:
+    """[T][2] = (sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod): the fp32 values of the schedule's buffers, on ``dev``, built once"""
+    tab = getattr(sched, "_diffuse_tab", None)
+    if tab is None or tab.device != dev:
+        tab = sched._diffuse_tab = torch.stack((sched.sqrt_alphas_cumprod, sched.sqrt_one_minus_alphas_cumprod), dim=1).to(dev).contiguous()
+    return tab
+
+
+def diffuse(x: torch.Tensor, noise: torch.Tensor, times: torch.Tensor, sched, *, normalize: bool, target=None):
+    """-> (x_t, target): ``x`` [B, ...] normalised to [-1, 1] when ``normalize``, corrupted to the timesteps ``times`` (int64 [B]) of ``sched``
+    with ``noise``, and what a U-Net that predicts ``target`` is compared with -- 'v': sqrt(abar) noise - sqrt(1 - abar) x0; 'x_start': the
+    normalised x0; 'noise': ``noise`` itself; None: nothing (the low-resolution conditioning image).  One mi_diffuse_fwd launch where
+    objective_active, the torch expressions of Imagen._p_losses otherwise: the same bits either way.  Not differentiable in ``x`` on the
+    kernel (the training loss never needs that)."""
+    if target not in _TARGET_KINDS:
+        raise ValueError(f"target must be one of 'noise', 'x_start', 'v' or None, got {target!r}")
+    if not objective_active(x):
+        x0 = x * 2 - 1 if normalize else x
+        x_t = sched.q_sample(x_start=x0, t=times, noise=noise)
+        return x_t, {None: None, 'noise': noise, 'x_start': x0}[target] if target != 'v' else sched.calculate_v(x0, times, noise)
+    xc, nc, tc = x.detach().contiguous(), noise.detach().contiguous(), times.contiguous()
+    if tc.dtype != torch.int64 or tc.shape != (xc.shape[0],) or nc.shape != xc.shape:
+        raise L.MinImagenHipError(f"diffuse: times must be int64 [{xc.shape[0]}] and noise shaped like x, got {tc.dtype} {tuple(tc.shape)}, {tuple(nc.shape)}")
+    tab = _diffuse_table(sched, xc.device)
+    L.require_device(xc, nc, tc, tab)
+    kind = _TARGET_KINDS[target]
+    x_t = torch.empty_like(xc)
+    tgt = torch.empty_like(xc) if kind else None
+    B = xc.shape[0]
+    p = L.MiDiffuseParams(B, xc.numel() // B, tab.shape[0], 1 if normalize else 0, kind, xc.data_ptr(), nc.data_ptr(), tc.data_ptr(), tab.data_ptr(),
+                          x_t.data_ptr(), L.ptr(tgt))
+    L.check(L.lib().mi_diffuse_fwd(C.byref(p), L.current_stream()), "mi_diffuse_fwd")
+    return x_t, (noise if target == 'noise' else tgt)
+
+
+class _ObjectiveLossFn(torch.autograd.Function):
+    """mi_objective_loss_fwd (+ its finish) and mi_objective_loss_bwd: the weighted loss as one fp32 on the device; when ``pred`` wants a
+    gradient the forward pass also writes g = w l'(d) / (B n) (saved for the backward, which is one launch: g * grad_out)"""
+
+    @staticmethod
+    def forward(ctx, pred, target, times, weights, loss_type):
+        lib = L.lib()
+        pc, tg = pred.detach().contiguous(), target.detach().contiguous()
+        tc = None if times is None else times.contiguous()
+        L.require_device(pc, tg, tc, weights)
+        B = pc.shape[0]
+        n = pc.numel() // B
+        dev = pc.device
+        partials = torch.empty(B * lib.mi_objective_chunks(n), dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        grad = torch.empty_like(pc) if ctx.needs_input_grad[0] else None          # (the no-grad evaluation has no gradient buffer)
+        p = L.MiObjectiveLossParams(B, n, _LOSS_KINDS[loss_type], 0 if weights is None else weights.numel(), pc.data_ptr(), tg.data_ptr(), L.ptr(tc),
+                                    L.ptr(weights), partials.data_ptr(), loss.data_ptr(), L.ptr(grad))
+        L.check(lib.mi_objective_loss_fwd(C.byref(p), L.current_stream()), "mi_objective_loss_fwd")
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (g,) = ctx.saved_tensors
+        go = grad_out.detach().to(torch.float32).contiguous()
+        L.require_device(go)
+        dpred = torch.empty_like(g)
+        L.check(L.lib().mi_objective_loss_bwd(g.data_ptr(), go.data_ptr(), dpred.data_ptr(), g.numel(), L.current_stream()), "mi_objective_loss_bwd")
+        return dpred, None, None, None, None
+
+
+def objective_loss(pred: torch.Tensor, target: torch.Tensor, times: torch.Tensor = None, weights: torch.Tensor = None, loss_type: str = 'l2') -> torch.Tensor:
+    """(1 / (B n)) sum_b w[times[b]] sum_i l(pred - target) as a scalar tensor, l = 'l1' | 'l2' | 'huber' (smooth-l1, beta = 1) and ``weights`` an
+    fp32 table [T] on the device of ``pred`` (GaussianDiffusion.loss_weight_table) or None for w = 1.  Differentiable in ``pred``.  On
+    objective.hip where objective_active (sums in fp64, no host synchronisation), else the same mathematics in torch ops."""
+    if loss_type not in _LOSS_KINDS:
+        raise ValueError(f"loss_type must be one of {tuple(_LOSS_KINDS)}, got {loss_type!r}")
+    if target.shape != pred.shape:
+        raise ValueError(f"objective_loss: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
+    if weights is not None and (times is None or times.dtype != torch.int64 or times.shape != (pred.shape[0],)):
+        raise ValueError("objective_loss: weights need times, int64 [B]")
+    if objective_active(pred):
+        if weights is not None and (weights.dtype != torch.float32 or weights.dim() != 1):
+            raise ValueError("objective_loss: weights must be float32 [T]")
+        return _ObjectiveLossFn.apply(pred, target, times, None if weights is None else weights.contiguous(), loss_type)
+    per = _LOSS_FNS[loss_type](pred, target, reduction='none').flatten(1).mean(dim=1)
+    if weights is not None:
+        per = per * weights[times]
+    return per.mean()
