@@ -62,7 +62,8 @@ typedef struct mi_act {
  * out = conv_k(act(concat(in0, in1*scale))) + bias [+ residual]
  *   act  = GroupNorm(groups) -> [x*(scale+1)+shift] -> SiLU   when gn_groups>0  (Block, layers.py:131-145)
  *   conv = k3 s1 p1 | k4 s2 p1 (Downsample, layers.py:319) | nearest x2 then k3 (Upsample, layers.py:512-515)
- *   residual = identity add of res0, or 1x1 conv (res_w) of concat(res0,res1*scale)  (ResnetBlock, layers.py:415,439)
+ *   residual = identity add of res0, or 1x1 conv (res_w) of concat(res0,res1*scale)  (ResnetBlock, layers.py:415,439),
+ *              or res0.scale*res0 + res1.scale*res1 (two Cout-channel tensors, no res_w: the guidance fold, tile_cfg 12)
  * Weights are pre-packed by the host: w[Cin][k][k][Cout_pad], Cout_pad = Cout rounded up to cout_tile.
  * The epilogue also emits the per-channel partial stats of `out` when out_stats != NULL.
  */
@@ -77,10 +78,15 @@ typedef struct mi_conv_params {
     const float* gn_gamma;  /* [Cin] */
     const float* gn_beta;   /* [Cin] */
     float gn_eps;
+    int ss_row1;            /* 0: one scale/shift row per image over all Cin channels (below).  != 0 (tile_cfg 12 with in1 only): in0's channels take
+                               row b (scale at ss_off+c, shift at ss_off+C0+c), in1's channels row b + ss_row1 (scale at ss_off+c-C0, shift at
+                               ss_off+C1+c-C0) -- two batch rows of one tensor as the two inputs (the guidance fold).  Sits in what was padding
+                               up to now: no offset and no size changed, zero-filled structs keep their meaning (added within ABI 12) */
     const float* scale_shift; /* [B][ss_stride]; scale at ss_off+c, shift at ss_off+Cin+c; NULL = none */
     int ss_stride, ss_off;
     mi_act res0, res1;      /* res0.data == NULL -> no residual */
-    const float* res_w;     /* [Cres][Cout_pad] 1x1 weights, NULL = identity */
+    const float* res_w;     /* [Cres][Cout_pad] 1x1 weights, NULL = identity; NULL with res1.data (tile_cfg 12 only, see mi_conv_stripe_rows): the weighted
+                               two-source identity residual res0.scale * res0 + res1.scale * res1 */
     const float* res_b;     /* [Cout] or NULL */
     float* out;             /* [B][Cout][H][W] */
     int out_st;             /* storage of `out` (as mi_act.st; single-term kernels only) */

@@ -29,7 +29,7 @@ class MiConvParams(C.Structure):
         ("in0", MiAct), ("in1", MiAct),
         ("Cout", C.c_int), ("ksize", C.c_int), ("stride", C.c_int), ("up2", C.c_int),
         ("w", C.c_void_p), ("bias", C.c_void_p),
-        ("gn_groups", C.c_int), ("gn_gamma", C.c_void_p), ("gn_beta", C.c_void_p), ("gn_eps", C.c_float),
+        ("gn_groups", C.c_int), ("gn_gamma", C.c_void_p), ("gn_beta", C.c_void_p), ("gn_eps", C.c_float), ("ss_row1", C.c_int),
         ("scale_shift", C.c_void_p), ("ss_stride", C.c_int), ("ss_off", C.c_int),
         ("res0", MiAct), ("res1", MiAct), ("res_w", C.c_void_p), ("res_b", C.c_void_p),
         ("out", C.c_void_p), ("out_st", C.c_int), ("out_stats", C.c_void_p), ("tile_cfg", C.c_int),

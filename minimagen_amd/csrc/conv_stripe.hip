@@ -78,6 +78,9 @@ namespace {
 // holds SOURCE rows of half the width, one new row per step, and the A-fragment indices go through (v >> 1) as in conv_rp's MODE 1.  Compile-time, because a residual load or an output store inside a run-time conditional makes the compiler's wait
 // counts conservative: the wait for step it's residual then also waits for the stores of step it - 1 and for the residual loads of step it + 1
 // that were issued a moment ago (seen in the ISA of the first version: vmcnt(3) .. (0) in every step).
+// 5 = the identity residual taken from TWO tensors, r0 * res0 + r1 * res1 (mi_act.scale of each): the guidance fold, where the two input octets and the
+// two residuals are the null and the conditional rows of one batch and the combine lives in the weights.  Two prefetched float4 streams instead of
+// one and two FMAs in the epilogue; compile-time like mode 1, for the same reason.
 // (Launches with a 1x1 residual conv stay on the tile kernel: the residual octets' ring rows would leave one workgroup per CU.)
 // RO_: channel octets of a 1x1 residual conv's input (ResnetBlock.res_conv over the block's input, layers.py:415,439): extra loader waves bring the two
 // rows of the step's own output positions (no halo: the centre tap only) into a 4-row ring of their own; one more MFMA triple per octet and group.
@@ -127,7 +130,9 @@ struct StCfg {
     // prologue units of the MFMA waves: the stripe's first 4 input rows, as half octets where that still fits one pass
     static constexpr bool PHS = HS && 2 * NPR * QPR * KO <= NCW * 64;
     static constexpr int PCH = PHS ? 4 : 8, PU = NPR * QPR * KO * (PHS ? 2 : 1);
-    static_assert(PU <= NCW * 64, "the MFMA waves transform the first four rows in one pass");
+    // (one pass everywhere but for two octets at 256 wide -- the guidance-fold member -- where the four rows are 512 units for 256 work-items)
+    static constexpr int PPASS = (PU + NCW * 64 - 1) / (NCW * 64);
+    static_assert(PPASS == 1 || (W_ == 256 && KO_ == 2 && PPASS == 2), "the MFMA waves transform the first four rows in one pass");
     static_assert(!DS || (LA > 0 && !GN_ && RO_ == 0 && W_ <= 128), "the stride-2 member is a plain conv, at most 128 output columns");
 };
 
@@ -400,9 +405,12 @@ __global__ __launch_bounds__(CFG::NT, CFG::WPE) void conv_stripe_kernel(const mi
             const int c = lane < Cin ? lane : 0;
             pg = p.gn_gamma[c];
             pb = p.gn_beta[c];
-            const float* ss = p.scale_shift ? p.scale_shift + (size_t)b * p.ss_stride + p.ss_off : p.gn_gamma;
-            ld_s1 = ss[p.scale_shift ? c : 0];
-            ld_s2 = ss[p.scale_shift ? Cin + c : 0];
+            // (ss_row1: in1's channels have a table row of their own, b + ss_row1, laid out over C1 channels -- two batch rows of one tensor as in0 / in1)
+            const bool split = p.scale_shift && p.ss_row1 != 0, second = split && c >= C0;
+            const int cs = second ? c - C0 : c, nsh = split ? (second ? C1 : C0) : Cin;
+            const float* ss = p.scale_shift ? p.scale_shift + ((long long)b + (second ? p.ss_row1 : 0)) * p.ss_stride + p.ss_off : p.gn_gamma;
+            ld_s1 = ss[p.scale_shift ? cs : 0];
+            ld_s2 = ss[p.scale_shift ? nsh + cs : 0];
         }
 #pragma unroll
         for (int jt = 0; jt < NJ; ++jt) {
@@ -428,17 +436,21 @@ __global__ __launch_bounds__(CFG::NT, CFG::WPE) void conv_stripe_kernel(const mi
         }
         // (d) the stripe's first four input rows (steps -1 and 0): one pixel quad x (half) octet per work-item
         constexpr int PCH = CFG::PCH, PHM = CFG::PHS ? 2 : 1;
-        const bool plive = ct < PU;
-        const int pu = plive ? ct : 0;
-        const int poct = pu / (NPR * QPR * PHM), phalf = PHM == 2 ? (pu / (NPR * QPR)) & 1 : 0, prow = (pu / QPR) % NPR, pq = pu % QPR;
-        f32x4 praw[PCH];
-        const int py = ys0 - 1 + prow;
-        const bool pin = py >= 0 && py < Hs;
-        {
-            const mi_gptr<const float> pbase = octet_base(poct) + (size_t)(PCH * phalf) * HWs;
-            const unsigned off = pin ? (unsigned)(py * WS + 4 * pq) : 0u;
+        constexpr int PPASS = CFG::PPASS;
+        bool plive[PPASS], pin[PPASS];
+        int poct[PPASS], phalf[PPASS], prow[PPASS], pq[PPASS];
+        f32x4 praw[PPASS][PCH];
 #pragma unroll
-            for (int j = 0; j < PCH; ++j) praw[j] = *reinterpret_cast<mi_gptr<const f32x4>>(pbase + (size_t)j * HWs + off);
+        for (int ps = 0; ps < PPASS; ++ps) {
+            plive[ps] = ct + ps * NCT < PU;
+            const int pu = plive[ps] ? ct + ps * NCT : 0;
+            poct[ps] = pu / (NPR * QPR * PHM); phalf[ps] = PHM == 2 ? (pu / (NPR * QPR)) & 1 : 0; prow[ps] = (pu / QPR) % NPR; pq[ps] = pu % QPR;
+            const int py = ys0 - 1 + prow[ps];
+            pin[ps] = py >= 0 && py < Hs;
+            const mi_gptr<const float> pbase = octet_base(poct[ps]) + (size_t)(PCH * phalf[ps]) * HWs;
+            const unsigned off = pin[ps] ? (unsigned)(py * WS + 4 * pq[ps]) : 0u;
+#pragma unroll
+            for (int j = 0; j < PCH; ++j) praw[ps][j] = *reinterpret_cast<mi_gptr<const f32x4>>(pbase + (size_t)j * HWs + off);
         }
         // the horizontal zero padding of the conv = a zero chunk left and right of every ring row
         for (int k = ct; k < KO * RING * 2; k += NCT) {
@@ -540,11 +552,12 @@ __global__ __launch_bounds__(CFG::NT, CFG::WPE) void conv_stripe_kernel(const mi
         if (cw == 0) ST_STAMP(4);
         __syncthreads();                                   // (3)
         if (cw == 0) ST_STAMP(5);
-        {
+#pragma unroll
+        for (int ps = 0; ps < PPASS; ++ps) {
             float4 PP[PCH];
 #pragma unroll
-            for (int j = 0; j < PCH; ++j) PP[j] = chP[8 * poct + PCH * phalf + j];
-            transform_quad(std::integral_constant<int, PCH>{}, praw, PP, pin, plive, poct, phalf, prow, pq);       // ring rows 0 .. 3 = input rows y0 - 1 .. y0 + 2
+            for (int j = 0; j < PCH; ++j) PP[j] = chP[8 * poct[ps] + PCH * phalf[ps] + j];
+            transform_quad(std::integral_constant<int, PCH>{}, praw[ps], PP, pin[ps], plive[ps], poct[ps], phalf[ps], prow[ps], pq[ps]);       // ring rows 0 .. 3 = input rows y0 - 1 .. y0 + 2
         }
 
         float bvv[NJ];
@@ -556,12 +569,13 @@ __global__ __launch_bounds__(CFG::NT, CFG::WPE) void conv_stripe_kernel(const mi
         }
         const int perm = ((lg & 1) << 1) | (lg >> 1);     // lane group -> input row (0, 2, 1, 3)
         const int dy = DS ? 0 : lq >> 3;
-        constexpr bool idres = CFG::OM == 1, MASKC = CFG::OM == 2 || DS;
+        constexpr bool idres2 = CFG::OM == 5, idres = CFG::OM == 1 || idres2, MASKC = CFG::OM == 2 || DS;
         const mi_gptr<float> obuf = mi_global(p.out + (size_t)b * p.Cout * HW);
         const mi_gptr<const float> rbuf = mi_global(idres ? p.res0.data + (size_t)mi_row_of(b, p.res0.bmod) * p.res0.C * HW : p.out);
         const float unscale = ldexpf(1.0f, -sExp[2]);
-        const float rs = idres ? p.res0.scale : 0.0f;
-        f32x4 rv[2][idres ? GPW : 1][idres ? NJ : 1];
+        const mi_gptr<const float> rbuf1 = mi_global(idres2 ? p.res1.data + (size_t)mi_row_of(b, p.res1.bmod) * p.res1.C * HW : p.out);
+        const float rs = idres ? p.res0.scale : 0.0f, rs1 = idres2 ? p.res1.scale : 0.0f;
+        f32x4 rv[2][idres ? GPW : 1][idres ? NJ : 1], rv1[2][idres2 ? GPW : 1][idres2 ? NJ : 1];
         auto issue_res = [&](int it, auto buf_tag) {       // identity residual of step it: unconditional loads (past the stripe: its last step again)
             constexpr int buf = decltype(buf_tag)::value;
             if constexpr (idres) {
@@ -573,6 +587,7 @@ __global__ __launch_bounds__(CFG::NT, CFG::WPE) void conv_stripe_kernel(const mi
                         const int co = 8 * jt + (lq & 7);
                         const int oy = y0 + 2 * itc + dy, ox = 16 * (cw * GPW + g) + 4 * lg;
                         rv[buf][g][jt] = *reinterpret_cast<mi_gptr<const f32x4>>(rbuf + (unsigned)(co * HW + oy * W + ox));
+                        if constexpr (idres2) rv1[buf][g][jt] = *reinterpret_cast<mi_gptr<const f32x4>>(rbuf1 + (unsigned)(co * HW + oy * W + ox));
                     }
             }
         };
@@ -730,6 +745,7 @@ __global__ __launch_bounds__(CFG::NT, CFG::WPE) void conv_stripe_kernel(const mi
                     y[0] = fmaf(acc[g][jt][0], unscale, bv); y[1] = fmaf(acc[g][jt][1], unscale, bv);
                     y[2] = fmaf(acc[g][jt][2], unscale, bv); y[3] = fmaf(acc[g][jt][3], unscale, bv);
                     if constexpr (idres) { const f32x4 r = rv[buf][g][jt]; y[0] = fmaf(r[0], rs, y[0]); y[1] = fmaf(r[1], rs, y[1]); y[2] = fmaf(r[2], rs, y[2]); y[3] = fmaf(r[3], rs, y[3]); }
+                    if constexpr (idres2) { const f32x4 r = rv1[buf][g][jt]; y[0] = fmaf(r[0], rs1, y[0]); y[1] = fmaf(r[1], rs1, y[1]); y[2] = fmaf(r[2], rs1, y[2]); y[3] = fmaf(r[3], rs1, y[3]); }
                     yv[g] = y;
                 }
                 if (first_of_block) {                      // statistics about a per-channel shift: the block's first value of the channel in this wave
@@ -816,7 +832,7 @@ int launch_stripe(const mi_conv_params& p, hipStream_t st) {
 
 template <int W>
 int launch_stripe_w(const mi_conv_params& p, hipStream_t st, int ko, int nj, bool gn) {
-    const int om = p.ksize == 4 ? 4 : (p.up2 ? 3 : (p.Cout < 8 * nj ? 2 : ((p.res0.data && !p.res_w) ? 1 : 0)));
+    const int om = p.ksize == 4 ? 4 : (p.up2 ? 3 : (p.Cout < 8 * nj ? 2 : ((p.res0.data && !p.res_w) ? (p.res1.data ? 5 : 1) : 0)));
     // the layer shapes of the BASELINE U-Nets: 8 / 16 / 24 / 32 input channels, 8 or 16 (or 3) output channels
 #define ST_BLOCK(KO, NJ) if (gn && ko == KO && nj == NJ) return om == 1 ? launch_stripe<W, KO, NJ, true, 1>(p, st) : launch_stripe<W, KO, NJ, true, 0>(p, st)
 #define ST_PLAIN(KO, NJ, OMV) if (!gn && ko == KO && nj == NJ && om == OMV) return launch_stripe<W, KO, NJ, false, OMV>(p, st)
@@ -825,6 +841,10 @@ int launch_stripe_w(const mi_conv_params& p, hipStream_t st, int ko, int nj, boo
     }
     if constexpr (W == 64) {                  // 16 -> 16 with the 1x1 residual conv over 32 channels (ups.0 of the SR U-Net): one workgroup per CU (105 KB of LDS)
         if (gn && ko == 2 && nj == 2 && om == 0 && p.res0.data && p.res_w) return launch_stripe<W, 2, 2, true, 0, 4>(p, st);
+    }
+    if constexpr (W == 64 || W == 256) {      // 8 + 8 -> 8 with the weighted two-source identity residual: final_res_block.block2 under the guidance fold
+        // (256 wide: 12 ring rows x 264 chunks x 32 B = 101 KB of LDS, one 8-wave workgroup per CU)
+        if (gn && ko == 2 && nj == 1 && om == 5) return launch_stripe<W, 2, 1, true, 5>(p, st);
     }
     if (om <= 1) {
         ST_BLOCK(1, 1);
@@ -857,6 +877,9 @@ int stripe_block_rows(const mi_conv_params& p, int* ko_, int* nj_) {
         const bool m8 = cres == 16 && C0 + C1 == 8 && p.Cout == 8 && (p.W == 64 || p.W == 128), m16 = ST_RO4 && cres == 32 && C0 + C1 == 16 && p.Cout == 16 && p.W == 64;
         if (!p.res_w_rp || (p.res0.C & 7) || (p.res1.data && (p.res1.C & 7)) || (p.res1.data && p.res1.st) || !(m8 || m16) || !p.gn_groups || p.up2) return 0;
     } else if (p.res0.data && p.res0.C != p.Cout) return 0;
+    const bool res2 = p.res0.data && p.res1.data && !p.res_w;      // weighted two-source identity residual: instantiated for 8 + 8 -> 8 behind a Block at 64 / 256 wide
+    if (res2 && (p.res1.C != p.Cout || p.res1.st || C0 != 8 || C1 != 8 || p.Cout != 8 || !p.gn_groups || p.up2 || ds || !(p.W == 64 || p.W == 256))) return 0;
+    if (p.ss_row1 && !p.in1.data) return 0;                        // a second scale/shift row belongs to a second input
     if (p.gn_groups > MI_MAX_GROUPS || (p.gn_groups > 0 && ((C0 + C1) % p.gn_groups))) return 0;
     if (p.gn_groups > 0 && (!p.in0.stats || (p.in1.data && !p.in1.stats))) return 0;
     const int ko = (C0 + C1) >> 3, nj = ds ? (p.Cout + 15) >> 4 : (p.Cout + 7) >> 3;
@@ -866,7 +889,7 @@ int stripe_block_rows(const mi_conv_params& p, int* ko_, int* nj_) {
         if (ko_) { *ko_ = ko; *nj_ = nj; }
         return sr0;
     }
-    const int om = p.up2 ? 3 : (p.Cout < 8 * nj ? 2 : ((p.res0.data && !rconv) ? 1 : 0));
+    const int om = p.up2 ? 3 : (p.Cout < 8 * nj ? 2 : ((p.res0.data && !rconv) ? (res2 ? 5 : 1) : 0));
     if (om == 3) {      // nearest x2 + conv (Upsample): 8 or 16 -> 8 channels, no GroupNorm, no residual, output at least 64 wide
         // (256-wide outputs stay on the tile kernel: write-bound, 52 against 48 us in the captured SR step; 128 wide: 20.8 against 27.8 us)
         if (gn || p.res0.data || nj != 1 || p.Cout != 8 || ko > 2 || p.W < 64 || p.W > 128 || (p.H & 1)) return 0;
@@ -875,7 +898,7 @@ int stripe_block_rows(const mi_conv_params& p, int* ko_, int* nj_) {
     }
     if ((om == 1 && !gn) || (om == 2 && (gn || nj != 1))) return 0;      // instantiated: identity residual behind a Block, masked channels in the final conv
     // the instantiated (ko, nj, gn) combinations of launch_stripe_w
-    const bool common = (ko == 1 && nj == 1) || (p.W <= 128 && ko == 2 && nj == 1 && gn);
+    const bool common = (ko == 1 && nj == 1) || (p.W <= 128 && ko == 2 && nj == 1 && gn && om != 5) || (ko == 2 && nj == 1 && gn && om == 5);
     const bool small = p.W <= 64 && ((ko == 2 && nj == 2 && gn) || (ko == 4 && nj == 2 && gn) || (ko == 1 && nj == 2 && !gn) || (ko == 3 && nj == 2 && gn));
     if (!common && !small) return 0;
     if (ko_) { *ko_ = ko; *nj_ = nj; }

@@ -34,6 +34,12 @@ FLASH_KV_PREP = os.environ.get("MINIMAGEN_FLASH_KV_PREP", "1") != "0"     # mult
 CE_MFMA = os.environ.get("MINIMAGEN_CE_MFMA", "1") != "0"                  # CrossEmbed on the matrix cores (0: the fp32 VALU kernel)
 ATTN_COND = os.environ.get("MINIMAGEN_ATTN_COND", "1") != "0"              # folded cross-attention contracted over cond_dim (variant 8: C in {8, 16}, cond_dim <= 8, fp32); 0: variant 6 with its per-head fragments and step tables
 INIT_DOWN = os.environ.get("MINIMAGEN_INIT_DOWN", "1") != "0"              # CrossEmbed + the first level's pre-Downsample as one launch (0: the two launches)
+# classifier-free guidance folded into the linear tail of the U-Net (final_res_block.block2 -> + residual -> final_conv): block2 reads the
+# null and the conditional rows as two input octets with the weights [(1 - s) W2 ; s W2] and writes B guided rows.
+# 0: the 2B-row tail and the combine in the sampler tail everywhere; 1: folded where the tail's time is bytes (images above 128 x 128: the
+# super-resolution stage); 2: folded wherever the library takes the shapes (the 64 x 64 base U-Net too: -3.4 % on the base stage, profiles/r16_cfg_fold.txt, but a bare base
+# workspace then holds B guided rows in ws.pred, which callers that combine the halves themselves do not expect)
+CFG_FOLD = int(os.environ.get("MINIMAGEN_CFG_FOLD", "1"))
 CONV_REVERSE = int(os.environ.get("MINIMAGEN_CONV_REVERSE", "1"))        # a row-paired conv walks the image groups opposite to its producer (0 = off)
 RP_NTILE = int(os.environ.get("MINIMAGEN_RP_NTILE", "0"))               # tiles per workgroup of the row-paired kernel (0 = the library's choice)
 RP_NTILE_BY = {k: int(os.environ.get("MINIMAGEN_RP_NTILE_" + k, "0")) for k in ("L", "M", "S")}     # ... per image-size class (> 128^2 / > 64^2 / smaller)
@@ -68,6 +74,12 @@ class Act:
     @property
     def st(self) -> int:
         return 1 if self.t.dtype == torch.bfloat16 else 0
+
+    def rows(self, lo: int, n: int) -> "Act":
+        """batch rows [lo, lo + n) as an activation of their own (the same storage)"""
+        a = Act(self.t[lo:lo + n], None if self.stats is None else self.stats[lo:lo + n], self.nt, self.C, self.H, self.W, n)
+        a.rev = self.rev
+        return a
 
     def c(self, consumer_batch: int, scale: float = 1.0) -> L.MiAct:
         bmod = self.batch if self.batch != consumer_batch else 0
@@ -533,13 +545,8 @@ class UnetEngine:
             nt_knob = RP_NTILE_BY[cls] or RP_NTILE
             if not nt_knob and ws.pipelined and RP_NTILE_PIPE[cls] and batch * nt // RP_NTILE_PIPE[cls] >= 256:
                 nt_knob = RP_NTILE_PIPE[cls]        # (only while the launch still has a workgroup per CU: smaller batches keep the library's choice -- config 3 at B = 16: 39.1 K with, 40.7 K without)
-            if stripe:                              # statistics blocks per workgroup of the stripe kernel (must divide the blocks of an image)
-                nt_knob = ST_NBLK[cls]
-                if ws.pipelined and ST_NBLK_PIPE[cls] and nt % ST_NBLK_PIPE[cls] == 0 and batch * nt // ST_NBLK_PIPE[cls] >= 128 \
-                        and self.unet.lowres_cond:       # (super-resolution U-Nets only: on the base U-Net it costs the base stage 7 %: 97.1 against 104.8 K steps/s, and gives the cascade nothing)
-                    nt_knob = ST_NBLK_PIPE[cls]
-                if nt_knob and (nt % nt_knob or nt_knob > 15):
-                    nt_knob = 0
+            if stripe:
+                nt_knob = self._stripe_nblk(ws, cls, nt, batch)
             p.tile_cfg |= (nt_knob & 0xf) << 12
             frags = pk.conv_ig if gemm else pk.conv_rp
             frag, p.w_rp_exp = frags[id(wpack)]
@@ -555,7 +562,81 @@ class UnetEngine:
         ws.prog.append((lib.mi_conv_fwd, p, "conv"))
         return out
 
-    def _emit_resnet(self, ws, pk, rb: ResnetBlock, in0: Act, in1: Optional[Act]) -> Act:
+    def _stripe_nblk(self, ws, cls, nt, batch) -> int:
+        """statistics blocks per workgroup of the stripe kernel (must divide the blocks of an image; 0 = the library's choice)"""
+        nt_knob = ST_NBLK[cls]
+        if ws.pipelined and ST_NBLK_PIPE[cls] and nt % ST_NBLK_PIPE[cls] == 0 and batch * nt // ST_NBLK_PIPE[cls] >= 128 \
+                and self.unet.lowres_cond:       # (super-resolution U-Nets only: on the base U-Net it costs the base stage 7 %: 97.1 against 104.8 K steps/s, and gives the cascade nothing)
+            nt_knob = ST_NBLK_PIPE[cls]
+        if nt_knob and (nt % nt_knob or nt_knob > 15):
+            nt_knob = 0
+        return nt_knob
+
+    # ------------------------------------------------------------------ guidance fold (DESIGN section 21)
+    def _cfg_fold_rows(self, ws, rb: ResnetBlock, x: Act) -> int:
+        """rows per statistics block of the folded final_res_block.block2 launch if this workspace takes the guidance fold, else 0"""
+        u = self.unet
+        if not CFG_FOLD or ws.B2 != 2 * ws.B or ws.half or u.init_conv_to_final_conv_residual or rb.cross_attn is not None \
+                or isinstance(rb.res_conv, nn.Conv2d) or x.batch != ws.B2 or (CFG_FOLD < 2 and x.H * x.W <= 128 * 128):
+            return 0
+        cls = "L" if x.H * x.W > 128 * 128 else ("M" if x.H * x.W > 64 * 64 else "S")
+        Cout = rb.block2.project.out_channels
+        if not CONV_RP or cls not in CONV_STRIPE or Cout != rb.block2.project.in_channels or Cout != x.C:
+            return 0
+        half = x.rows(0, ws.B)
+        return self._stripe_rows(ws.B, x.H, x.W, half, half, Cout, SimpleNamespace(num_groups=2 * rb.block2.groupnorm.num_groups), (half, half, None, None))
+
+    def _emit_cfg_fold(self, ws, pk, rb: ResnetBlock, h: Act, x: Act, rows: int) -> Act:
+        """final_res_block.block2 of a guidance batch as ONE B-row launch over [null rows ; conditional rows] (conditional rows first in the
+        batch): out = conv(act(concat(h_null, h_cond))) + b + (1 - s) x_null + s x_cond with the weights [(1 - s) W2 ; s W2] -- the weights,
+        the two residual factors and nothing else depend on s (set_guidance)."""
+        lib, B = L.lib(), ws.B
+        conv, gn = rb.block2.project, rb.block2.groupnorm
+        Cout, H, W = conv.out_channels, h.H, h.W
+        nt = H // rows
+        out = self._new_act(ws, B, Cout, H, W, nt)
+        if not hasattr(pk, "cfg_fold_gn"):            # the groups stay inside their half: 2 x groups over gamma | gamma
+            pk.cfg_fold_gn = (torch.cat((gn.weight.detach(), gn.weight.detach())).contiguous(), torch.cat((gn.bias.detach(), gn.bias.detach())).contiguous())
+            pk.cfg_fold_w = {}
+        p = L.MiConvParams()
+        p.B, p.H, p.W = B, H, W
+        p.in0, p.in1 = h.rows(B, B).c(B), h.rows(0, B).c(B)
+        p.Cout, p.ksize, p.stride, p.up2 = Cout, 3, 1, 0
+        p.bias = L.ptr(conv.bias)
+        p.gn_groups, p.gn_gamma, p.gn_beta, p.gn_eps = 2 * gn.num_groups, L.ptr(pk.cfg_fold_gn[0]), L.ptr(pk.cfg_fold_gn[1]), gn.eps
+        ss_off = pk.ss_off.get(id(rb))
+        if ss_off is not None:                        # in0 = the null rows [B, 2B) of the step's table, in1 = the conditional rows B above them
+            p.scale_shift, p.ss_stride, p.ss_off, p.ss_row1 = L.ptr(ws.ss[B:]), ws.ss.shape[1], ss_off, -B
+        p.res0, p.res1 = x.rows(B, B).c(B), x.rows(0, B).c(B)
+        cls = "L" if H * W > 128 * 128 else ("M" if H * W > 64 * 64 else "S")
+        p.out, p.out_stats, p.tile_cfg = L.ptr(out.t), L.ptr(out.stats), 12 | 0x100 | ((self._stripe_nblk(ws, cls, nt, B) & 0xf) << 12)
+        out.rev = bool(CONV_REVERSE) and B % 8 == 0 and not h.rev
+        if out.rev:
+            p.tile_cfg |= 0x200
+        ws.cfg_fold = SimpleNamespace(p=p, conv=conv, scale=None)
+        self.set_guidance(ws, 1.0)                    # a fresh workspace is runnable: [0 ; W2] reproduces the conditional prediction
+        ws.prog.append((lib.mi_conv_fwd, p, "conv"))
+        return out
+
+    def set_guidance(self, ws, cond_scale: float):
+        """Point the folded block2 launch of ``ws`` (if it has one) at the weights composed for ``cond_scale`` and set its residual factors.
+        Host-only but for the first use of a scale; launches already enqueued or captured keep the values they were issued with."""
+        fold = getattr(ws, "cfg_fold", None)
+        s = float(cond_scale)
+        if fold is None or fold.scale == s:
+            return
+        pk = self.packed()
+        ent = pk.cfg_fold_w.get(s)
+        if ent is None:
+            while len(pk.cfg_fold_w) >= 16:
+                pk.cfg_fold_w.pop(next(iter(pk.cfg_fold_w)))
+            ent = pk.cfg_fold_w[s] = P.pack_conv_weight_rp(P.compose_cfg_fold(fold.conv.weight, s))
+        p = fold.p
+        p.w_rp, p.w_rp_exp = L.ptr(ent[0]), ent[1]
+        p.res0.scale, p.res1.scale = 1.0 - s, s
+        fold.scale, fold.keep = s, ent
+
+    def _emit_resnet(self, ws, pk, rb: ResnetBlock, in0: Act, in1: Optional[Act], cfg_fold_rows: int = 0) -> Act:
         """layers.py:417-439"""
         u = self.unet
         s = u.skip_connect_scale
@@ -565,6 +646,8 @@ class UnetEngine:
                             gn=rb.block1.groupnorm, want_stats=not has_cross, skip_scale=s)
         if has_cross:
             h = self._emit_cross_attn(ws, pk, rb.cross_attn.fn, h)
+        if cfg_fold_rows and h.batch == ws.B2:
+            return self._emit_cfg_fold(ws, pk, rb, h, in0, cfg_fold_rows)
         ss_off = pk.ss_off.get(id(rb))
         if isinstance(rb.res_conv, nn.Conv2d):
             res = (in0, in1, pk.conv[id(rb.res_conv)], rb.res_conv.bias)
@@ -929,9 +1012,11 @@ class UnetEngine:
             if isinstance(upsample, nn.Sequential):
                 cv = upsample[1]
                 cur = self._emit_conv(ws, pk, cur, None, wpack=pk.conv[id(cv)], bias=cv.bias, Cout=cv.out_channels, up2=1)
-        cur = self._emit_resnet(ws, pk, u.final_res_block, cur, None)
+        ws.cfg_fold = None
+        cur = self._emit_resnet(ws, pk, u.final_res_block, cur, None, cfg_fold_rows=self._cfg_fold_rows(ws, u.final_res_block, cur))
+        # (under the guidance fold `cur` holds B guided rows, and so does the prediction: the sampler tail runs without the combine)
         out = self._emit_conv(ws, pk, cur, None, wpack=pk.conv[id(u.final_conv)], bias=u.final_conv.bias, Cout=u.channels_out,
-                              want_stats=False, conditioned=True, out_fp32=True)       # the prediction feeds the (fp32, bit-exact) sampler
+                              want_stats=False, conditioned=ws.cfg_fold is None, out_fp32=True)       # the prediction feeds the (fp32, bit-exact) sampler
         ws.pred = out.t
         if (out.H, out.W) != (H, W):
             raise L.MinImagenHipError(f"U-Net output is {out.H}x{out.W} for a {H}x{W} input (image size must be divisible by the down-sampling factor)")
@@ -1128,8 +1213,10 @@ class UnetEngine:
         if two:
             keep = torch.cat((torch.ones(B, dtype=torch.bool), torch.zeros(B, dtype=torch.bool)))
         self.set_text(ws, text_embeds, text_mask, keep)
+        if two:
+            self.set_guidance(ws, cond_scale)
         self.run(ws)
-        if not two:
+        if not two or ws.cfg_fold is not None:
             return ws.pred.clone()
         out = torch.empty(B, u.channels_out, H, W, dtype=torch.float32, device=ws.dev)
         p = L.MiCfgX0Params(B, u.channels_out * H * W, L.ptr(ws.pred), 1, float(cond_scale), 0, 0, 0, L.ptr(out), 0)

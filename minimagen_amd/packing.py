@@ -70,6 +70,14 @@ def rp_weight_exponent(mx: float) -> int:
     return max(-100, min(100, exp))
 
 
+def compose_cfg_fold(w2: torch.Tensor, cond_scale: float) -> torch.Tensor:
+    """Classifier-free guidance folded into a linear conv: (1 - s) conv(a_null) + s conv(a_cond) = conv'(concat(a_null, a_cond)) with
+    W' = [(1 - s) W ; s W] over the input channels, composed in fp64 (the fragment packer picks its power-of-two exponent from W')."""
+    w = w2.detach().double()
+    s = float(cond_scale)
+    return torch.cat(((1.0 - s) * w, s * w), 1).contiguous()
+
+
 def pack_conv_weight_rp(w: torch.Tensor, exp=None):
     """[Cout][Cin][3][3] (or [Cout][Cres][1][1]) fp32 -> (fragments, exponent) for csrc/conv_rp.hip.
 

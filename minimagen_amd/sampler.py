@@ -221,6 +221,8 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
     n = Cc * H * W
     T = noise_scheduler.num_timesteps if solver is None else solver[0]
     two = ws.B2 != ws.B
+    eng.set_guidance(ws, cond_scale)
+    combine = two and ws.cfg_fold is None          # guidance folded into the U-Net's tail: ws.pred holds B guided rows
     if begun is None:
         begun = stage_begin(unet, shape, noise_scheduler=noise_scheduler, ws=ws, noise_fn=noise_fn, seed=seed, sample0=sample0, stage=stage, solver=solver, max_states=max_states,
                             inpaint=inpaint, objective=objective)
@@ -245,7 +247,7 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
         st.seed_dev.fill_(seed)
     if entry is None:
         # the radix select's first pass rides on the producer of x0; st.hist is zero on allocation and every mi_quantile_fwd leaves it zeroed again
-        cp = L.MiCfgX0Params(B, n, L.ptr(ws.pred), 1 if two else 0, float(cond_scale), L.ptr(ws.x), L.ptr(st.coef), L.ptr(st.t_state), 0, L.ptr(st.x0), L.ptr(st.hist))
+        cp = L.MiCfgX0Params(B, n, L.ptr(ws.pred), 1 if combine else 0, float(cond_scale), L.ptr(ws.x), L.ptr(st.coef), L.ptr(st.t_state), 0, L.ptr(st.x0), L.ptr(st.hist))
         qp = L.MiQuantileParams(B, n, L.ptr(st.x0), k_lo, k_hi, w, L.ptr(st.hist), L.ptr(st.s_q), L.ptr(st.v_q), 1, 1)
         pp = L.MiPosteriorParams(B, n, T, L.ptr(st.x0), L.ptr(st.s_q), L.ptr(ws.x), L.ptr(st.coef), L.ptr(st.t_state),
                                  L.ptr(noise_dev), seed, sample0, stage << 20, L.ptr(st.seed_dev) if noise_dev is None else 0)

@@ -1,6 +1,6 @@
 """Development aid: time ONE conv launch shape of the SR / base U-Net in isolation on the GPU (HIP events, back to back) and, with the
 -DMI_TRACE build of the library (MINIMAGEN_HIP_LIB=.../libminimagen_hip_trace.so), print the per-phase shader-clock breakdown of
-conv_rp.hip.   python tools/bench_conv.py B Cin Cout H W gn res(none|id|conv) path(rp6|rp7|rp12: full-width stripes|old|w6|w7|w10: the wide regime) [C1]"""
+conv_rp.hip.   python tools/bench_conv.py B Cin Cout H W gn res(none|id|id2: the guidance fold's two-source residual, with C1|conv) path(rp6|rp7|rp12: full-width stripes|old|w6|w7|w10: the wide regime) [C1]"""
 import ctypes as C
 import os
 import sys
@@ -54,12 +54,15 @@ def run(B, C0, Cout, H, W, gn, res, path, C1=0, reps=20, nt_in=None):
         cfg = (0 if (W >= 64 and H * W > 64 * 64) else 2) | 0x100 | (0x800 if H * W <= 64 * 64 else 0)
     p.bias = bias.data_ptr()
     if gn:
-        p.gn_groups, p.gn_gamma, p.gn_beta, p.gn_eps = 8, gamma.data_ptr(), beta.data_ptr(), 1e-5
+        p.gn_groups, p.gn_gamma, p.gn_beta, p.gn_eps = (16 if res == "id2" else 8), gamma.data_ptr(), beta.data_ptr(), 1e-5
         if not all(s_ is not None for s_ in (s0,)):
             raise SystemExit("GroupNorm needs statistics")
     if res == "id":
         r = torch.randn(B, Cout, H, W, generator=g).to(dev); keep.append(r)
         p.res0 = L.MiAct(r.data_ptr(), Cout, 0, 0, 1.0, 0)
+    elif res == "id2":                             # r0 * res0 + r1 * res1 (csrc/conv_stripe.hip output mode 5)
+        r, r1 = torch.randn(B, Cout, H, W, generator=g).to(dev), torch.randn(B, Cout, H, W, generator=g).to(dev); keep += [r, r1]
+        p.res0, p.res1 = L.MiAct(r.data_ptr(), Cout, 0, 0, -2.0, 0), L.MiAct(r1.data_ptr(), Cout, 0, 0, 3.0, 0)
     elif res == "conv":
         r = torch.randn(B, Cin, H, W, generator=g).to(dev); keep.append(r)
         rs = stats(r); keep.append(rs)
@@ -107,7 +110,7 @@ def run(B, C0, Cout, H, W, gn, res, path, C1=0, reps=20, nt_in=None):
         L.check(lib.mi_conv_fwd(C.byref(p), st), "conv")
     e1.record(); torch.cuda.synchronize()
     us = e0.elapsed_time(e1) / reps * 1e3
-    mb = (B * (Cin + Cout + (Cout if res == "id" else (Cin if res == "conv" else 0))) * H * W * 4) / 1e6
+    mb = (B * (Cin + Cout + (Cout if res == "id" else (2 * Cout if res == "id2" else (Cin if res == "conv" else 0)))) * H * W * 4) / 1e6
     tf = 2.0 * (Cin * 9 + (Cin if res == "conv" else 0)) * Cout * H * W * B / us * 1e-6
     print(f"{path:5s}{' wide' if wide else ''} B{B} {Cin}->{Cout} @{H}x{W} gn={int(gn)} res={res}: {us:7.1f} us  ({mb:.0f} MB -> {mb / us * 1e-3 * 1e3:.2f} GB/ms; {tf:.0f} TFLOP/s algorithmic, x3 split terms issued)")
     if path.startswith("rp") and hasattr(lib, "mi_debug_read_trace_rp"):
