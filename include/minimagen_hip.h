@@ -190,11 +190,14 @@ typedef struct mi_linear {   /* torch nn.Linear layout: w[out][in], b[out] (b ma
  * time-token rows): text_to_cond -> truncate/pad to max_len -> mask / CFG-drop to null_text_embed
  * -> mean-pool -> to_text_non_attn_cond (LayerNorm, Linear, SiLU, Linear) -> null_text_hidden
  * select; and norm_cond (LayerNorm, per row) of the text rows of c.  Row b' of the outputs uses
- * text row b' % B and keep[b'] (the all-True / all-False prob_mask_like of Unet.py:587). */
+ * text row b' % B and keep[b'] (the all-True / all-False prob_mask_like of Unet.py:587).
+ * text_rows (in what was padding behind max_len: the struct and the ABI are unchanged) = 0 or B: as above; = B2: row b' uses text row b' of
+ * text_embeds [B2][L][E] / text_mask [B2][L] -- a negative prompt is the rows [B, B2) with keep = 1; anything else MI_ERR_INVALID. */
 typedef struct mi_text_cond_params {
     int B2, B, L, E, cd, tcd, max_len;
-    const float* text_embeds;       /* [B][L][E] */
-    const uint8_t* text_mask;       /* [B][L] or NULL (all valid) */
+    int text_rows;                  /* 0 | B | B2: rows of text_embeds / text_mask */
+    const float* text_embeds;       /* [B][L][E] ([B2][L][E] with text_rows = B2) */
+    const uint8_t* text_mask;       /* [B][L] ([B2][L]) or NULL (all valid) */
     const uint8_t* keep;            /* [B2] */
     mi_linear text_to_cond;
     const float* null_text_embed;   /* [max_len][cd] */
@@ -819,6 +822,29 @@ typedef struct {
 int mi_objective_loss_fwd(const mi_objective_loss_params* p, void* stream);
 /* dpred[i] = g[i] * *grad_out for i < count, grad_out read from device memory (the backward of mi_objective_loss_fwd: g is its `grad`) */
 int mi_objective_loss_bwd(const float* g, const float* grad_out, float* dpred, long long count, void* stream);
+
+/* ---- guidance rescale (Lin et al. 2023, eq. 15-16), between the U-Net and the sampler tail of a guided step ---------------------
+ * Per image, with c = pred2[b] and u = pred2[B + b] (the null or negative-prompt prediction):
+ *     g = u + (c - u) * cond_scale        rounded as the tails' combine rounds it (subtract, multiply, add: three roundings)
+ *     f = rescale * sigma(c) / sigma(g) + (1 - rescale)       sigma over the n elements of the image; f = 1 when sigma(g) == 0
+ *     pred2[b] <- g * f                   one fp32 rounding of f, one of the product; rows [B, 2B) are not written
+ * so that a tail with two = 0 reads B finished rows.  Two launches over (mi_cfg_rescale_chunks(n), B), no atomics, no workgroup waits for
+ * another: stats writes partials[(b * chunks + k) * 4 + {0..3}] = sum c, sum c^2, sum g, sum g^2 of chunk k (fp64 throughout, a fixed
+ * order); apply re-adds an image's rows in index order, forms sigma^2 = Q / n - (S / n)^2 (clamped at 0) and f in fp64 and rewrites the row.
+ * An image's result depends on its own 2 n values alone: not on B, its position in the batch or the launch.  A NaN or inf anywhere in an
+ * image's two rows makes its row [b] NaN.  16-byte accesses when n % 4 == 0 and pred2 is 16-byte aligned, element by element otherwise.
+ * MI_ERR_INVALID: B or n not positive, B > 65535, n > 2^30, NULL pred2 / partials, rescale outside [0, 1], cond_scale not finite.
+ * Struct index 33 of mi_struct_size; added within ABI 12 (no existing entry changed). */
+#define MI_CFG_RESCALE_CHUNK 4096
+typedef struct mi_cfg_rescale_params {
+    int B, n;
+    float* pred2;                   /* [2B][n]: conditional rows [0, B), null / negative rows [B, 2B); rows [0, B) are OVERWRITTEN with g * f */
+    float cond_scale, rescale;
+    double* partials;               /* [B][mi_cfg_rescale_chunks(n)][4], device scratch */
+} mi_cfg_rescale_params;
+int mi_cfg_rescale_chunks(int n);   /* ceil(n / MI_CFG_RESCALE_CHUNK) */
+int mi_cfg_rescale_stats_fwd(const mi_cfg_rescale_params* p, void* stream);
+int mi_cfg_rescale_apply_fwd(const mi_cfg_rescale_params* p, void* stream);
 
 /* ---- HIP graphs: capture a sequence of the calls above once, replay it per timestep ------- */
 int mi_graph_begin(void* stream);

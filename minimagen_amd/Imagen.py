@@ -291,6 +291,52 @@ class Imagen(nn.Module):
             inpaint = (inpaint_images, m.to(torch.uint8))
         return start, stop, inpaint, start_image
 
+    def _parse_guidance(self, batch_size: int, cond_scale, texts, text_embeds, text_masks, negative_texts, negative_text_embeds,
+                        negative_text_masks, guidance_rescale):
+        """-> (phi: 0. when off, negative captions: None, a list of ``batch_size`` strings, or (embeds, mask or None) still where the caller has
+        them).  Host only; raises ValueError on bad or inconsistent values."""
+        phi = 0.
+        if guidance_rescale is not None:
+            if isinstance(guidance_rescale, bool) or not isinstance(guidance_rescale, (int, float)) or not 0. <= float(guidance_rescale) <= 1.:
+                raise ValueError(f"guidance_rescale must be a number in [0, 1], got {guidance_rescale!r}")
+            phi = float(guidance_rescale)
+        negative = None
+        if negative_texts is not None and negative_text_embeds is not None:
+            raise ValueError("pass negative_texts or negative_text_embeds, not both")
+        if negative_text_masks is not None and negative_text_embeds is None:
+            raise ValueError("negative_text_masks goes with negative_text_embeds")
+        masked = exists(text_masks) or not exists(text_embeds)              # (captions encoded here always come with masks)
+        if negative_texts is not None:
+            if isinstance(negative_texts, str):
+                negative_texts = [negative_texts] * batch_size
+            if not isinstance(negative_texts, (list, tuple)) or not all(isinstance(t, str) for t in negative_texts):
+                raise ValueError("negative_texts must be a string or a list of strings")
+            if len(negative_texts) != batch_size:
+                raise ValueError(f"negative_texts: batch {len(negative_texts)} does not match the text batch {batch_size}")
+            if not masked:
+                raise ValueError("negative_texts are encoded with masks: pass text_masks with text_embeds (the captions and the negative captions "
+                                 "must both carry masks, or neither)")
+            negative = list(negative_texts)
+        elif negative_text_embeds is not None:
+            e, m = negative_text_embeds, negative_text_masks
+            if not torch.is_tensor(e) or e.dim() != 3 or not e.is_floating_point():
+                raise ValueError("negative_text_embeds must be a float tensor [B, L, E]")
+            if e.shape[0] != batch_size:
+                raise ValueError(f"negative_text_embeds: batch {e.shape[0]} does not match the text batch {batch_size}")
+            if e.shape[2] != self.text_embed_dim:
+                raise ValueError(f"negative_text_embeds: embedding dimension {e.shape[2]}, the model has {self.text_embed_dim}")
+            if m is not None and (not torch.is_tensor(m) or tuple(m.shape) != tuple(e.shape[:2])):
+                raise ValueError(f"negative_text_masks must be a tensor {tuple(e.shape[:2])} like negative_text_embeds")
+            if masked != (m is not None):
+                raise ValueError("negative prompts: the captions and the negative captions must both carry masks, or neither")
+            if m is None and exists(text_embeds) and text_embeds.shape[1] != e.shape[1]:
+                raise ValueError(f"negative prompts: unmasked captions of different lengths ({text_embeds.shape[1]} and {e.shape[1]}) cannot be "
+                                 "joined; pass masks")
+            negative = (e.detach(), None if m is None else m.detach())
+        if (phi or negative is not None) and cond_scale == 1.:
+            raise ValueError("negative prompts and guidance_rescale need cond_scale != 1: at 1 the second half of the guidance batch is never evaluated")
+        return phi, negative
+
     def _lowres_conditioning(self, unet: Unet, img, image_size: int, ws, lowres_noise_level: float, noise_fn, seed, sample0, stage):
         """Imagen.py:479-485 + :393: cubic resize (reflect pad) -> q_sample at int(T*level) -> *2-1."""
         lib = L.lib()
@@ -319,7 +365,9 @@ class Imagen(nn.Module):
                _use_graph: bool = True, _precision: str = None, _async: bool = False, _revalidated: bool = False,
                sample_steps: Union[int, List[int], Tuple[int, ...]] = None, sampler: str = None, sampler_eta: float = None,
                inpaint_images: torch.Tensor = None, inpaint_masks: torch.Tensor = None, start_image: torch.Tensor = None,
-               start_at_stage: int = None, stop_at_stage: int = None):
+               start_at_stage: int = None, stop_at_stage: int = None,
+               negative_texts: Union[str, List[str]] = None, negative_text_embeds: torch.Tensor = None, negative_text_masks: torch.Tensor = None,
+               guidance_rescale: float = None):
         """minimagen/Imagen.py:424-510.  Private keyword-only extras (not in the reference): ``_noise(shape)`` injects a
         host noise stream in the reference's draw order (parity runs); otherwise noise is Philox keyed by
         (``_seed``, ``_sample_offset`` + row, stage, step, element) so a sharded batch reproduces the unsharded one;
@@ -346,12 +394,27 @@ class Imagen(nn.Module):
 
         A stage whose U-Net was built with ``pred_objectives`` 'v' or 'x_start' samples from a coefficient table whose columns 0 and 1 turn
         that prediction into x0 (GaussianDiffusion.sampler_coef_table), for every setting above; nothing else differs, and a 'noise' stage is
-        untouched."""
+        untouched.
+
+        More of classifier-free guidance (keyword-only, not in the reference; both need ``cond_scale`` != 1).  Negative
+        prompts: ``negative_texts`` (B strings, or one for every row; encoded like ``texts``) or ``negative_text_embeds`` [B, Ln, E] with an
+        optional ``negative_text_masks`` [B, Ln] -- the rows of the guidance batch that see the learned null embeddings otherwise are
+        conditioned on that caption, and the result is neg + (pos - neg) * cond_scale.  Ln may differ from the captions' length only when
+        both sides carry masks (the shorter is padded with zero embeddings under a False mask); both sides masked, or neither.
+        ``guidance_rescale`` = phi in [0, 1] (Lin et al. 2023; None and 0: off): per image, the guided prediction g is scaled to the standard
+        deviation of the conditional prediction c and mixed with itself, g * (phi * std(c) / std(g) + 1 - phi), on what the U-Net predicts
+        (whatever its objective), before x0 and the dynamic threshold.  Both go with every setting above.  Bad values raise ValueError
+        before anything is launched; a call with neither goes through exactly the workspaces, states, graphs and kernels it went through
+        before they existed.  Nothing here has been tried on a trained model: what is checked is the arithmetic."""
         solvers = self._parse_solver(sample_steps, sampler, sampler_eta)
+        rescale, negative = 0., None
         if exists(text_embeds) or exists(texts):
             first_stage, end_stage, inpaint, start_image = self._parse_inpaint(text_embeds.shape[0] if exists(text_embeds) else len(texts), inpaint_images,
                                                                                inpaint_masks, start_image, start_at_stage, stop_at_stage)
-        call_args = dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, start_image=start_image, start_at_stage=start_at_stage,
+            rescale, negative = self._parse_guidance(text_embeds.shape[0] if exists(text_embeds) else len(texts), cond_scale, texts, text_embeds, text_masks,
+                                                     negative_texts, negative_text_embeds, negative_text_masks, guidance_rescale)
+        call_args = dict(negative_texts=negative_texts, negative_text_embeds=negative_text_embeds, negative_text_masks=negative_text_masks,
+                         guidance_rescale=guidance_rescale, inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, start_image=start_image, start_at_stage=start_at_stage,
                          stop_at_stage=stop_at_stage, sample_steps=sample_steps, sampler=sampler, sampler_eta=sampler_eta, texts=texts, text_masks=text_masks, text_embeds=text_embeds, cond_scale=cond_scale, lowres_sample_noise_level=lowres_sample_noise_level,
                          return_pil_images=return_pil_images, device=device, _noise=_noise, _seed=_seed, _sample_offset=_sample_offset,
                          _use_graph=_use_graph, _precision=_precision, _async=_async)
@@ -363,6 +426,8 @@ class Imagen(nn.Module):
             text_embeds, text_masks = t5_encode_text(texts, name=self.text_encoder_name)
             text_embeds, text_masks = map(lambda t: t.to(device), (text_embeds, text_masks))
         assert exists(text_embeds), 'text or text encodings must be passed into Imagen'
+        if isinstance(negative, list):
+            negative = t5_encode_text(negative, name=self.text_encoder_name)
         assert not (exists(text_embeds) and text_embeds.shape[-1] != self.text_embed_dim), \
             f'invalid text embedding dimension being passed in (should be {self.text_embed_dim})'
         assert not (cond_scale != 1. and not self.can_classifier_guidance), \
@@ -380,6 +445,10 @@ class Imagen(nn.Module):
         if start_image is not None:
             start_image = start_image.to(device).contiguous()
         pixel_inputs = [t for t in (inpaint or ())[:2] + (start_image,) if t is not None]
+        if negative is not None:            # read by the stage streams like the captions (record_stream below)
+            negative = tuple(None if t is None else t.to(device) for t in negative)
+            pixel_inputs += [t for t in negative if t is not None]
+        neg_text = {} if negative is None else dict(negative_embeds=negative[0], negative_mask=negative[1])
 
         # One HIP stream PER STAGE (graphs cannot be captured on the legacy default stream anyway).  Within a call stage s + 1 waits for
         # stage s through an event; ACROSS calls the stages form a pipeline: with ``_async=True`` the caller's stream is never made to
@@ -433,6 +502,8 @@ class Imagen(nn.Module):
         # ... and neither does a noise-predicting stage: only another objective names itself (it selects the stage's coefficient table)
         extras = {stage: dict(known, **({} if self.pred_objectives[stage] == 'noise' else dict(objective=self.pred_objectives[stage])))
                   for stage, _ in stages}
+        # guidance rescale reads both halves of the prediction: a workspace of its own that never folds the guidance into the U-Net's tail
+        unfolded, rescaled = ({}, {}) if not rescale else (dict(fold=False), dict(rescale=rescale))
         # ---- pass 1, every stage on its own stream: what depends on the CAPTIONS only (text conditioning, the folded context rows, x_T, the
         # step tables) -- issued for all stages up front, so a later stage has it behind it when its low-resolution input arrives
         wss, begun = {}, {}
@@ -449,8 +520,8 @@ class Imagen(nn.Module):
                 eng = unet.engine()
                 # per call, never sticky engine state: a later Unet.forward stays on the engine's default precision
                 ws = wss[stage] = eng.workspace(batch_size, B2, image_size, image_size, precision=precision, lane=lane,
-                                                pipelined=bool(_async and on_gpu and SAMPLE_LANES > 1))
-                eng.set_text(ws, text_embeds, text_masks, keep)
+                                                pipelined=bool(_async and on_gpu and SAMPLE_LANES > 1), **unfolded)
+                eng.set_text(ws, text_embeds, text_masks, keep, **neg_text)
                 if unet.lowres_cond:             # the augmentation level's timestep feeds the step tables (diffusion_model.py:68-69)
                     ws.lowres_times.fill_(int(self.lowres_noise_schedule.num_timesteps * lowres_sample_noise_level))
                 if _noise is None:
@@ -469,7 +540,7 @@ class Imagen(nn.Module):
                     self._lowres_conditioning(unet, img, image_size, ws, lowres_sample_noise_level, _noise, _seed, _sample_offset, stage)
                 img = self._p_sample_loop(unet, (batch_size, self.channels, image_size, image_size), noise_scheduler=noise_scheduler,
                                           ws=ws, cond_scale=cond_scale, noise_fn=_noise, seed=_seed, sample0=_sample_offset,
-                                          stage=stage, use_graph=_use_graph, begun=begun.get(stage), solver=solvers[stage], **extras[stage])
+                                          stage=stage, use_graph=_use_graph, begun=begun.get(stage), solver=solvers[stage], **extras[stage], **rescaled)
                 if on_gpu:
                     prev_done = streams[stage].record_event()
         pack_tokens = [] if (_noise is not None or _revalidated) else [(unet.engine(), unet.engine().pack_begin()) for unet in self.unets]

@@ -67,7 +67,7 @@ class MiLinear(C.Structure):
 class MiTextCondParams(C.Structure):
     _fields_ = [
         ("B2", C.c_int), ("B", C.c_int), ("L", C.c_int), ("E", C.c_int), ("cd", C.c_int), ("tcd", C.c_int), ("max_len", C.c_int),
-        ("text_embeds", C.c_void_p), ("text_mask", C.c_void_p), ("keep", C.c_void_p),
+        ("text_rows", C.c_int), ("text_embeds", C.c_void_p), ("text_mask", C.c_void_p), ("keep", C.c_void_p),
         ("text_to_cond", MiLinear), ("null_text_embed", C.c_void_p), ("ln_w", C.c_void_p), ("ln_b", C.c_void_p),
         ("h1", MiLinear), ("h2", MiLinear), ("null_text_hidden", C.c_void_p), ("norm_w", C.c_void_p), ("norm_b", C.c_void_p),
         ("c_text", C.c_void_p), ("text_hiddens", C.c_void_p),
@@ -233,6 +233,10 @@ class MiObjectiveLossParams(C.Structure):
                 ("loss", C.c_void_p), ("grad", C.c_void_p), ("reserved", C.c_longlong * 2)]
 
 
+class MiCfgRescaleParams(C.Structure):
+    _fields_ = [("B", C.c_int), ("n", C.c_int), ("pred2", C.c_void_p), ("cond_scale", C.c_float), ("rescale", C.c_float), ("partials", C.c_void_p)]
+
+
 class MiPackConv3Desc(C.Structure):
     _fields_ = [("w", C.c_void_p), ("frag", C.c_void_p), ("generic", C.c_void_p), ("Cout", C.c_int), ("Cin", C.c_int), ("adjoint", C.c_int),
                 ("exp", C.c_int), ("cout_pad", C.c_int), ("reserved", C.c_int)]
@@ -242,7 +246,7 @@ _STRUCTS = {0: MiAct, 1: MiConvParams, 2: MiCrossEmbedParams, 3: MiLinear, 4: Mi
             6: MiAttnFoldParams, 7: MiCrossAttnParams, 8: MiCfgX0Params, 9: MiQuantileParams, 10: MiPosteriorParams,
             11: MiResizeParams, 12: MiSelfAttnParams, 13: MiChanFFParams, 14: MiFlashAttnParams, 15: MiTokensToNchwParams, 16: MiConvWgradParams, 17: MiBlockBwdParams, 18: MiCrossEmbedWgradParams, 19: MiFoldedAttnParams, 20: MiAdamTensor, 21: MiAdamParams, 22: MiPackConv3Desc,
             23: MiFlashAttnTrainParams, 24: MiSamplerExtParams, 25: MiInpaintParams, 26: MiInitDownParams, 27: MiAttnCondParams,
-            28: MiEmaTensor, 29: MiEmaParams, 31: MiDiffuseParams, 32: MiObjectiveLossParams}
+            28: MiEmaTensor, 29: MiEmaParams, 31: MiDiffuseParams, 32: MiObjectiveLossParams, 33: MiCfgRescaleParams}
 
 _lib = None
 _backend = None
@@ -276,6 +280,11 @@ def _bind(lib):
     lib.mi_objective_loss_bwd.argtypes = [vp, vp, vp, C.c_longlong, vp]
     lib.mi_objective_chunks.argtypes = [i32]
     for name in ("mi_diffuse_fwd", "mi_objective_loss_fwd", "mi_objective_loss_bwd", "mi_objective_chunks"):
+        getattr(lib, name).restype = i32
+    lib.mi_cfg_rescale_chunks.argtypes = [i32]
+    lib.mi_cfg_rescale_stats_fwd.argtypes = [vp, vp]
+    lib.mi_cfg_rescale_apply_fwd.argtypes = [vp, vp]
+    for name in ("mi_cfg_rescale_chunks", "mi_cfg_rescale_stats_fwd", "mi_cfg_rescale_apply_fwd"):
         getattr(lib, name).restype = i32
     lib.mi_conv_prep_bytes.argtypes = [i32, i32, i32, i32, i32]
     lib.mi_conv_prep_bytes.restype = C.c_longlong

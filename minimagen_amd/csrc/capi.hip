@@ -58,6 +58,7 @@ extern "C" int mi_struct_size(int which) {
         case 29: return (int)sizeof(mi_ema_params);
         case 31: return (int)sizeof(mi_diffuse_params);             // (30 stays unassigned)
         case 32: return (int)sizeof(mi_objective_loss_params);
+        case 33: return (int)sizeof(mi_cfg_rescale_params);
     }
     return -1;
 }

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void text_cond_kernel(const mi_text_cond_param
     __shared__ __attribute__((aligned(16))) float pooled[MI_MAX_CD];
     __shared__ __attribute__((aligned(16))) float hid[MI_MAX_TCD];
     const int tid = threadIdx.x, NT = 256;
-    const int bb = blockIdx.x, b = bb % p.B;
+    const int bb = blockIdx.x, b = p.text_rows == p.B2 ? bb : bb % p.B;       // a text row per guidance row (negative prompts) | per sample
     const bool keep = p.keep[bb] != 0;
     float* crow = p.c_text + (size_t)bb * p.max_len * p.cd;
     // 1. projected / null tokens (pre-norm) -> c_text
@@ -270,6 +270,7 @@ extern "C" int mi_attn_fragment_floats(int C) { return ((C / 4) < 4 ? 4 : (C / 4
 
 extern "C" int mi_text_cond_fwd(const mi_text_cond_params* p, void* stream) {
     if (p->cd > MI_MAX_CD || p->tcd > MI_MAX_TCD || p->B2 <= 0 || p->B <= 0) { mi_set_error("mi_text_cond_fwd: cd/tcd too large or empty batch"); return MI_ERR_INVALID; }
+    if (p->text_rows != 0 && p->text_rows != p->B && p->text_rows != p->B2) { mi_set_error("mi_text_cond_fwd: text_rows %d is neither 0, B = %d nor B2 = %d", p->text_rows, p->B, p->B2); return MI_ERR_INVALID; }
     hipLaunchKernelGGL(text_cond_kernel, dim3(p->B2), dim3(256), 0, (hipStream_t)stream, *p);
     return mi_check_launch("text_cond_kernel");
 }

@@ -55,7 +55,9 @@ def sample_distributed(imagen, *, text_embeds: torch.Tensor, text_masks: Optiona
     ``sample_steps`` / ``sampler`` / ``sampler_eta``, ...): the noise is keyed by the global row, the stage and the STEP index, so the
     gathered batch equals the unsharded call bit for bit for every solver and step count.  The per-row pixel inputs ``inpaint_images`` /
     ``inpaint_masks`` / ``start_image`` are passed full-batch as well and sharded by the same row bounds (the known-region draws are keyed
-    like the step noise); ``start_at_stage`` / ``stop_at_stage`` go through (the gathered images then have the last stage's size that ran)."""
+    like the step noise); ``start_at_stage`` / ``stop_at_stage`` go through (the gathered images then have the last stage's size that ran).
+    ``negative_text_embeds`` / ``negative_text_masks`` (full batch) are sharded by the same bounds; ``guidance_rescale`` goes through (its
+    statistics are per image, so sharding changes no bit)."""
     ws = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     batch = text_embeds.shape[0]
@@ -68,7 +70,7 @@ def sample_distributed(imagen, *, text_embeds: torch.Tensor, text_masks: Optiona
         size = imagen.image_sizes[(sample_kwargs.get("stop_at_stage") or len(imagen.image_sizes)) - 1]
         local = torch.zeros(0, imagen.channels, size, size, dtype=torch.float32, device=dev)
         return gather_samples(local, batch, group) if (gather and not _alone(ws)) else local
-    for name in ("inpaint_images", "inpaint_masks", "start_image"):
+    for name in ("inpaint_images", "inpaint_masks", "start_image", "negative_text_embeds", "negative_text_masks"):
         if sample_kwargs.get(name) is not None:
             sample_kwargs[name] = sample_kwargs[name][lo:hi].contiguous()
     local = imagen.sample(text_embeds=text_embeds[lo:hi].contiguous(),

@@ -97,6 +97,32 @@ def _lin(m: Optional[nn.Linear]) -> L.MiLinear:
     return L.MiLinear(L.ptr(m.weight), L.ptr(m.bias) if m.bias is not None else 0, m.in_features, m.out_features)
 
 
+def join_negative(embeds: torch.Tensor, mask: Optional[torch.Tensor], neg_embeds: torch.Tensor, neg_mask: Optional[torch.Tensor]):
+    """-> (embeds [2B, L, E], mask [2B, L] or None): the captions of a guidance batch whose rows [B, 2B) see a negative prompt.  Lengths may
+    differ only when both sides carry masks: the shorter side is padded with zero embeddings under a False mask (masked rows become null
+    embeddings).  Without masks every row of a caption stays, the reference's zero padding comes AFTER the projection (Unet.py:581-603) and
+    zero embeddings before it are not the same thing -- so unmasked inputs of different lengths, or one side masked and the other not, raise
+    ValueError.  Host-only checks on shapes; the tensors stay where they are."""
+    if neg_embeds.dim() != 3 or neg_embeds.shape[0] != embeds.shape[0] or neg_embeds.shape[2] != embeds.shape[2]:
+        raise ValueError(f"negative_text_embeds {tuple(neg_embeds.shape)} does not match the text embeddings {tuple(embeds.shape)} in batch and dimension")
+    if (mask is None) != (neg_mask is None):
+        raise ValueError("negative prompts: the captions and the negative captions must both carry masks, or neither")
+    if neg_mask is not None and tuple(neg_mask.shape) != tuple(neg_embeds.shape[:2]):
+        raise ValueError(f"negative_text_masks {tuple(neg_mask.shape)} does not match negative_text_embeds {tuple(neg_embeds.shape)}")
+    Lp, Ln = embeds.shape[1], neg_embeds.shape[1]
+    if Lp != Ln and mask is None:
+        raise ValueError(f"negative prompts: unmasked captions of different lengths ({Lp} and {Ln}) cannot be joined; pass masks")
+    Lm = max(Lp, Ln)
+
+    def pad(e, m):
+        if e.shape[1] == Lm:
+            return e, m
+        return (torch.cat((e, e.new_zeros(e.shape[0], Lm - e.shape[1], e.shape[2])), dim=1),
+                torch.cat((m, m.new_zeros(m.shape[0], Lm - m.shape[1])), dim=1))
+    (e0, m0), (e1, m1) = pad(embeds, mask), pad(neg_embeds.to(embeds.dtype), neg_mask)
+    return torch.cat((e0, e1)).contiguous(), (None if mask is None else torch.cat((m0.to(torch.bool), m1.to(torch.bool))).contiguous())
+
+
 class Workspace:
     """Attribute bag of one (shape, precision, lane): buffers, launch plan (``prog*``) and what the sampling loop caches on it."""
 
@@ -368,15 +394,16 @@ class UnetEngine:
         return self._pack if self._pack is not None else self.pack()
 
     def workspace(self, B: int, B2: int, H: int, W: int, precision: Optional[str] = None, has_text: bool = True, lane: int = 0,
-                  pipelined: bool = False) -> Workspace:
+                  pipelined: bool = False, fold: bool = True) -> Workspace:
         """``lane``: independent workspaces (buffers, step tables, captured graphs) of one shape, so that two sample() calls can be in
         flight side by side (Imagen.sample(_async=True) alternates lanes); ``pipelined``: the launch plan of calls that share the GPU with
-        another lane (strip lengths RP_NTILE_PIPE; same results, another workspace)"""
+        another lane (strip lengths RP_NTILE_PIPE; same results, another workspace); ``fold=False``: a workspace of its own that never takes
+        the guidance fold -- ws.pred keeps BOTH halves of the prediction (guidance rescale reads them)"""
         pk = self.packed()
         dev = next(self.unet.parameters()).device
         precision = self.precision if precision is None else precision
         assert precision in ("fp32", "half"), precision
-        key = (B, B2, H, W, str(dev), precision, has_text) + ((lane,) if lane else ()) + (("pipe",) if pipelined else ())
+        key = (B, B2, H, W, str(dev), precision, has_text) + ((lane,) if lane else ()) + (("pipe",) if pipelined else ()) + (() if fold else ("nofold",))
         ws = self._ws.get(key)
         if ws is not None:
             return ws
@@ -384,6 +411,7 @@ class UnetEngine:
         ws = Workspace()
         ws.B, ws.B2, ws.H, ws.W, ws.dev = B, B2, H, W, dev
         ws.pipelined = pipelined
+        ws.no_fold = not fold
         ws.half = precision == "half"
         f = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
         ws.x = f(B, u.channels, H, W)
@@ -576,7 +604,7 @@ class UnetEngine:
     def _cfg_fold_rows(self, ws, rb: ResnetBlock, x: Act) -> int:
         """rows per statistics block of the folded final_res_block.block2 launch if this workspace takes the guidance fold, else 0"""
         u = self.unet
-        if not CFG_FOLD or ws.B2 != 2 * ws.B or ws.half or u.init_conv_to_final_conv_residual or rb.cross_attn is not None \
+        if not CFG_FOLD or ws.no_fold or ws.B2 != 2 * ws.B or ws.half or u.init_conv_to_final_conv_residual or rb.cross_attn is not None \
                 or isinstance(rb.res_conv, nn.Conv2d) or x.batch != ws.B2 or (CFG_FOLD < 2 and x.H * x.W <= 128 * 128):
             return 0
         cls = "L" if x.H * x.W > 128 * 128 else ("M" if x.H * x.W > 64 * 64 else "S")
@@ -1025,8 +1053,11 @@ class UnetEngine:
             ws.prog_cond += self._fold_params(ws, pk, ws.c_time, ws.ntot * u.cond_dim, 1, ws.ntot, 0)
 
     # ------------------------------------------------------------------ execution
-    def set_text(self, ws, text_embeds: torch.Tensor, text_mask: Optional[torch.Tensor], keep: torch.Tensor):
-        """K2 + the step-invariant part of the context fold.  Once per ``sample()`` / ``forward``."""
+    def set_text(self, ws, text_embeds: torch.Tensor, text_mask: Optional[torch.Tensor], keep: torch.Tensor,
+                 negative_embeds: Optional[torch.Tensor] = None, negative_mask: Optional[torch.Tensor] = None):
+        """K2 + the step-invariant part of the context fold.  Once per ``sample()`` / ``forward``.  ``negative_embeds`` [B, Ln, E] (with
+        ``negative_mask`` [B, Ln] when ``text_mask`` is given: join_negative) conditions the rows [B, 2B) of a guidance workspace on a caption
+        of their own: ONE [2B, L, E] text tensor, text_rows = B2 and keep = 1 on every row, whatever ``keep`` says."""
         u, pk, lib = self.unet, self.packed(), L.lib()
         st = L.current_stream()
         if text_embeds is None:
@@ -1038,6 +1069,11 @@ class UnetEngine:
         assert ws.has_text, "workspace was built for a call without text"
         text_embeds = text_embeds.to(device=ws.dev, dtype=torch.float32).contiguous()
         assert text_embeds.shape[0] == ws.B and text_embeds.shape[-1] == u.text_embed_dim
+        if negative_embeds is not None:
+            assert ws.B2 == 2 * ws.B, "negative captions need a guidance workspace (B2 = 2 B)"
+            text_embeds, text_mask = join_negative(text_embeds, None if text_mask is None else text_mask.to(device=ws.dev), negative_embeds.to(device=ws.dev, dtype=torch.float32),
+                                                   None if negative_mask is None else negative_mask.to(device=ws.dev))
+            keep = torch.ones(ws.B2, dtype=torch.bool)
         mask8 = None if text_mask is None else text_mask.to(device=ws.dev).to(torch.uint8).contiguous()
         # a host -> device copy from pageable memory blocks the host behind everything queued on this stream (the previous call's stage,
         # in the pipelined sampler): skip it when the guidance pattern is the one already on the device (every sampling call)
@@ -1050,6 +1086,7 @@ class UnetEngine:
         p = L.MiTextCondParams()
         p.B2, p.B, p.L, p.E, p.cd, p.tcd, p.max_len = ws.B2, ws.B, text_embeds.shape[1], u.text_embed_dim, u.cond_dim, u.time_cond_dim, MAX_TEXT_LEN
         p.text_embeds, p.text_mask, p.keep = L.ptr(text_embeds), L.ptr(mask8), L.ptr(ws.keep)
+        p.text_rows = text_embeds.shape[0] if negative_embeds is not None else 0
         p.text_to_cond = _lin(u.text_to_cond)
         p.null_text_embed = L.ptr(u.null_text_embed)
         ln = u.to_text_non_attn_cond[0]

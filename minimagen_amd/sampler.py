@@ -54,13 +54,14 @@ class StageState:
     ``hw`` (pixels per channel plane) makes it the state of an INPAINTING call -- an entry of its own: the coefficient table with columns 6 and
     7, and the known-image / mask buffers every call copies into (so one captured graph serves every later call's images and masks);
     ``ip`` (None otherwise) is the kernels' block over them, rebuilt by every stage_begin.  ``objective`` (what the stage's U-Net predicts: 'noise',
-    'x_start' or 'v') only chooses columns 0 and 1 of the coefficient table: no kernel, struct or launch knows about it."""
+    'x_start' or 'v') only chooses columns 0 and 1 of the coefficient table: no kernel, struct or launch knows about it.
+    ``rescale_partials`` (None until a call with guidance_rescale > 0 runs on this state): the [B][chunks][4] fp64 sums of mi_cfg_rescale_*."""
     __slots__ = ("coef", "tau", "t_map", "x0_prev", "ext", "t_state", "x0", "hist", "s_q", "v_q", "seed_dev", "graphs",
-                 "group_sync", "group_err_host", "group_failed", "group_heal", "known", "mask", "ip", "known_noise")
+                 "group_sync", "group_err_host", "group_failed", "group_heal", "known", "mask", "ip", "known_noise", "rescale_partials")
 
     def __init__(self, sched, B: int, n: int, dev, solver=None, hw: int = None, objective: str = 'noise'):
         self.tau = self.t_map = self.x0_prev = None     # the reference's loop has no step -> timestep map and no history
-        self.known = self.mask = self.ip = self.known_noise = None
+        self.known = self.mask = self.ip = self.known_noise = self.rescale_partials = None
         known = {} if hw is None else dict(known=True)
         if objective != 'noise':
             known['objective'] = objective
@@ -211,18 +212,22 @@ def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream):
 
 def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, noise_fn=None, seed: int = 0, sample0: int = 0,
                   stage: int = 0, use_graph: bool = True, begun=None, solver=None, group_max: int = 8, max_states: int = 8, inpaint=None,
-                  objective: str = 'noise'):
+                  objective: str = 'noise', rescale: float = 0.):
     """Imagen.py:373-420 + :329-370 + :261-326: T replays of [U-Net (both guidance halves) -> CFG combine + x0 -> dynamic-threshold quantile ->
     posterior draw -> t -= 1].  ``solver`` = (S, sampler, eta): S steps over a subsequence of the trained timesteps; the loop, the noise index and the
     Philox stream count STEPS: the reference's loop with T = S but for the state's step -> timestep map and history buffer (``st.ext``).
-    ``objective``: what the U-Net predicts; it selects the stage state (its coefficient table) and nothing else."""
+    ``objective``: what the U-Net predicts; it selects the stage state (its coefficient table) and nothing else.
+    ``rescale`` = phi > 0 (guidance rescale; on a workspace built with fold=False): two launches between the U-Net and the tail
+    leave the rescaled guided prediction in rows [0, B) of ws.pred, and the tail runs as it does behind a folded U-Net."""
     lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
     B, Cc, H, W = shape
     n = Cc * H * W
     T = noise_scheduler.num_timesteps if solver is None else solver[0]
     two = ws.B2 != ws.B
     eng.set_guidance(ws, cond_scale)
-    combine = two and ws.cfg_fold is None          # guidance folded into the U-Net's tail: ws.pred holds B guided rows
+    rescale = float(rescale)
+    assert not rescale or (two and ws.cfg_fold is None), "guidance rescale reads both halves of the prediction"
+    combine = two and ws.cfg_fold is None and not rescale        # guidance folded into the U-Net's tail / rescaled in place: ws.pred holds B guided rows
     if begun is None:
         begun = stage_begin(unet, shape, noise_scheduler=noise_scheduler, ws=ws, noise_fn=noise_fn, seed=seed, sample0=sample0, stage=stage, solver=solver, max_states=max_states,
                             inpaint=inpaint, objective=objective)
@@ -238,7 +243,7 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
         st.group_sync.zero_()               # stream-ordered behind every launch queued on this lane: ticket, counters, histograms, error word
         st.group_heal = False
     # the captured graph of `per` steps is cached per (workspace, guidance, threshold, noise mode, shard offset, tail kind); the seed is in device memory
-    gkey = (float(cond_scale), two, k_lo, k_hi, w, sample0, stage, T, noise_dev is None, group) + (() if solver is None else (tuple(solver),)) + (() if st.ip is None else ("inpaint",))
+    gkey = (float(cond_scale), two, k_lo, k_hi, w, sample0, stage, T, noise_dev is None, group) + (() if solver is None else (tuple(solver),)) + (() if st.ip is None else ("inpaint",)) + ((("rescale", rescale),) if rescale else ())
     entry = st.graphs.get(gkey) if (use_graph and noise_dev is None) else None
     seed = int(seed) & 0x7FFFFFFFFFFFFFFF
     if noise_dev is None:
@@ -255,9 +260,17 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
             st.group_sync = torch.zeros(lib.mi_sampler_group_sync_bytes(B, n), dtype=torch.uint8, device=ws.dev)   # this workspace's launches only
             st.group_err_host = torch.zeros(1, dtype=torch.int32).pin_memory() if L.backend() == "hip-gfx950" else torch.zeros(1, dtype=torch.int32)
         launch, advance = tail_launcher(st, ws, kind, cp, qp, pp, stream)
+        rp = None
+        if rescale:                              # phi and the scale are baked into the launches (gkey)
+            if st.rescale_partials is None:
+                st.rescale_partials = torch.zeros(B, lib.mi_cfg_rescale_chunks(n), 4, dtype=torch.float64, device=ws.dev)
+            rp = C.byref(L.MiCfgRescaleParams(B, n, L.ptr(ws.pred), float(cond_scale), rescale, L.ptr(st.rescale_partials)))
 
         def one_step(k=0, by=1):                 # step *t_state - k, then the device-resident step moves by `by`
             eng.run_step(ws, stream, t_off=k)
+            if rp is not None:
+                L.check(lib.mi_cfg_rescale_stats_fwd(rp, stream), "mi_cfg_rescale_stats_fwd")
+                L.check(lib.mi_cfg_rescale_apply_fwd(rp, stream), "mi_cfg_rescale_apply_fwd")
             launch(k)
             if by:
                 advance(by)
