@@ -629,7 +629,7 @@ __global__ __launch_bounds__(256) void ln_tokens_kernel(const mi_act x, int HW, 
 }
 
 // Same operand scheme as cross_attn_folded_kernel (16 tokens per wave), but the context (HW+1 rows) is walked in
-// chunks of JTC tiles with an online softmax: running max m, running sum l, O_h rescaled by 2^(m_old - m_new).
+// chunks of JTC tiles with an online softmax: running max m, running sum l, O_h = O_h 2^(m_old - m_new) + the chunk's P V.
 template <int C, int JTC>
 __global__ __launch_bounds__(256) void self_attn_folded_kernel(const mi_self_attn_params p, const int JT) {
     constexpr int KK = C / 4, NGP = KK < 4 ? 4 : KK, MT = (C + 15) / 16, FR = NGP + 4 * MT;
@@ -663,7 +663,9 @@ __global__ __launch_bounds__(256) void self_attn_folded_kernel(const mi_self_att
     const int jlast = p.J - 1;
     for (int h = 0; h < p.heads; ++h) {
         const float* gvh = gvb + (size_t)h * JT * 64 * FR;
-        f32x4 oh[MT];
+        // blocked summation: P V of each chunk is accumulated from zero (oc) and joins the running O_h with one FMA per register (one chain
+        // over all J rows let the fp32 rounding grow with sqrt(J): 6 x the unfolded fp32 evaluation's error at 4096 tokens)
+        f32x4 oh[MT], oc[MT];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) oh[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
         float m = -INFINITY, l = 0.0f;
@@ -706,9 +708,7 @@ __global__ __launch_bounds__(256) void self_attn_folded_kernel(const mi_self_att
             l = l * alpha + cl;
             m = mn;
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) oh[mt][r] *= alpha;
+            for (int mt = 0; mt < MT; ++mt) oc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int t = 0; t < JTC; ++t) {
                 if (jt0 + t < JT) {
@@ -721,9 +721,13 @@ __global__ __launch_bounds__(256) void self_attn_folded_kernel(const mi_self_att
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) oh[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vw[4 * mt + r], s[t][r], oh[mt], 0, 0, 0);
+                        for (int r = 0; r < 4; ++r) oc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vw[4 * mt + r], s[t][r], oc[mt], 0, 0, 0);
                 }
             }
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) oh[mt][r] = fmaf(oh[mt][r], alpha, oc[mt][r]);
         }
         const float linv = 1.0f / l;
 #pragma unroll

@@ -201,7 +201,8 @@ __device__ __forceinline__ void mi_stat_finish(const mi_stat_acc& a, double& S, 
     Q = fma(c, fma(n, c, 2.0 * s), (double)a.q);             // sum (d + c)^2 = sum d^2 + 2 c sum d + n c^2
 }
 // one value per lane: (sum, sum of squares) over the 16 lanes lq = 0 .. 15 of this lane's group (valid at lq == 0) / over the whole wave
-// (valid in every lane), shifted by the group's / wave's first lane's value
+// (valid in every lane).  fp32 only inside a 16-lane group, shifted by the group's first lane's value; the four groups of a wave are added
+// in fp64.  (One fp32 sum over all 64 lanes about lane 0's value lost a digit of the record whenever that value was an outlier of the tile.)
 __device__ __forceinline__ void mi_stat_reduce16(float y, bool ok, int lane, double& S, double& Q) {
     mi_stat_acc a;
     a.c = __shfl(y, lane & 48);
@@ -214,13 +215,15 @@ __device__ __forceinline__ void mi_stat_reduce16(float y, bool ok, int lane, dou
 }
 __device__ __forceinline__ void mi_stat_reduce64(float y, bool ok, double& S, double& Q) {
     mi_stat_acc a;
-    a.c = __shfl(y, 0);
+    a.c = __shfl(y, 0, 16);
     a.s = ok ? y - a.c : 0.0f;
     a.q = a.s * a.s;
-    a.n = ok ? 1 : 0;
+    a.n = __popcll((__ballot(ok) >> (threadIdx.x & 48)) & 0xffffull);      // the group's count from one ballot (1-D workgroups of whole waves)
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { a.s += __shfl_xor(a.s, o); a.q += __shfl_xor(a.q, o); a.n += __shfl_xor(a.n, o); }
+    for (int o = 1; o < 16; o <<= 1) { a.s += __shfl_xor(a.s, o); a.q += __shfl_xor(a.q, o); }
     mi_stat_finish(a, S, Q);
+#pragma unroll
+    for (int o = 16; o < 64; o <<= 1) { S += __shfl_xor(S, o); Q += __shfl_xor(Q, o); }
 }
 
 // global-memory accessors with the address space pinned (see mi_global)
