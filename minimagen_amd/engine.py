@@ -21,6 +21,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from . import conv_route as R
 from . import packing as P
 from .layers import Attention, CrossAttention, EinopsToAndFrom, Identity, Parallel, ResnetBlock, TransformerBlock
 
@@ -59,6 +60,11 @@ ST_NBLK = {k: int(os.environ.get("MINIMAGEN_ST_NBLK_" + k, "0")) for k in ("L", 
 ST_NBLK_PIPE = {k: int(os.environ.get("MINIMAGEN_ST_NBLK_PIPE_" + k, d)) for k, d in (("L", "0"), ("M", "0"), ("S", "4"))}
 WEIGHT_FINGERPRINT = os.environ.get("MINIMAGEN_WEIGHT_FINGERPRINT", "1") != "0"   # content fingerprint of the weights at every public call (see pack())
 JT = 17     # context tiles of 16 rows: 1 null + (2|4) time tokens + 256 text rows <= 272
+
+
+def _conv_knobs() -> dict:
+    """the conv knobs above as they stand NOW (tests patch them), for conv_route"""
+    return {name: globals()[name] for name in R.KNOBS}
 
 
 class Act:
@@ -451,33 +457,20 @@ class UnetEngine:
         self._ws[key] = ws
         return ws
 
-    def _tile_cfg(self, H, W, batch=None, cz=1):
-        """Tile shape by image size ONLY: the per-tile partial statistics must reduce in the same order whatever the
-        batch is, so that a sharded batch reproduces the unsharded rows bit for bit."""
-        lib = L.lib()
-        best = 0 if (W >= 64 and H * W > 64 * 64) else 2
-        th, tw = C.c_int(), C.c_int()
-        lib.mi_conv_tile_shape(best, C.byref(th), C.byref(tw))
-        return best, -(-H // th.value) * -(-W // tw.value)
-
     def _stripe_rows(self, batch, Ho, Wo, in0, in1, Cout, gn, res, up2=0, ksize=3, stride=1) -> int:
         """rows per statistics block if csrc/conv_stripe.hip (tile_cfg 12) takes this narrow fp32 k3 s1 (or k4 s2) launch, else 0: asked of the library
         (mi_conv_stripe_rows) on a probe of the launch's shape -- pointers only need to be non-null where the real launch has them"""
+        def probe(a: Optional[Act]) -> L.MiAct:
+            return L.MiAct() if a is None else L.MiAct(1, a.C, 1 if a.stats is not None else 0, a.nt, 1.0, 0)
+        r0, r1, rw, _ = res if res is not None else (None,) * 4
         q = L.MiConvParams()
         q.B, q.H, q.W, q.Cout, q.ksize, q.stride, q.up2 = batch, Ho, Wo, Cout, ksize, stride, int(bool(up2))
-        q.in0 = L.MiAct(1, in0.C, 1 if in0.stats is not None else 0, in0.nt, 1.0, 0)
-        if in1 is not None:
-            q.in1 = L.MiAct(1, in1.C, 1 if in1.stats is not None else 0, in1.nt, 1.0, 0)
+        q.in0, q.in1, q.res0, q.res1 = probe(in0), probe(in1), probe(r0), probe(r1)
         q.w_rp = 1
         if gn is not None:
             q.gn_groups = gn.num_groups
-        if res is not None:
-            r0, r1, rw, _ = res
-            q.res0 = L.MiAct(1, r0.C, 1 if r0.stats is not None else 0, r0.nt, 1.0, 0)
-            if r1 is not None:
-                q.res1 = L.MiAct(1, r1.C, 1 if r1.stats is not None else 0, r1.nt, 1.0, 0)
-            if rw is not None:
-                q.res_w, q.res_w_rp = 1, 1
+        if rw is not None:
+            q.res_w, q.res_w_rp = 1, 1
         return int(L.lib().mi_conv_stripe_rows(C.byref(q)))
 
     def _new_act(self, ws, batch, Cc, H, W, nt, fp32: bool = False) -> Act:
@@ -494,51 +487,21 @@ class UnetEngine:
         Wo = in0.W * 2 if up2 else in0.W // stride
         if stride == 2 and ((in0.H | in0.W) & 1):
             raise NotImplementedError("stride-2 conv on an odd-sized image")
-        ins = [a for a in (in0, in1) if a is not None] + ([r for r in res[:2] if r is not None] if res else [])
-        batch = ws.B2 if (conditioned or any(a.batch == ws.B2 for a in ins)) else ws.B
-        ct = lib.mi_conv_cout_tile(Cout)
-        cfg, nt = self._tile_cfg(Ho, Wo, batch, -(-Cout // ct))
-        cin_tot = in0.C + (in1.C if in1 is not None else 0)
-        # row-paired matrix-core path (conv_rp.hip): every conv whose channel counts come in octets.  Narrow layers (<= 64 in, <= 32 out: the
-        # BASELINE U-Nets) run the tuned single-kernel form; wider ones (Unet() default, Base, Super) the wide regime: output channels
-        # tiled over the grid, GroupNorm affine + operand exponents from a small per-image launch (mi_gn_coef_fwd) ahead of the conv
-        cres = 0 if (res is None or res[2] is None) else res[0].C + (res[1].C if res[1] is not None else 0)
-        rp = bool(CONV_RP) and ((ksize == 3 and stride == 1) or (ksize == 4 and stride == 2 and not up2 and CONV_RP >= 2)) \
-            and (not up2 or CONV_RP >= 2) and Wo % 4 == 0 and id(wpack) in pk.conv_rp \
-            and in0.C % 8 == 0 and (in1 is None or in1.C % 8 == 0) \
-            and (res is None or res[2] is None or (id(res[2]) in pk.conv_rp and res[0].C % 8 == 0 and (res[1] is None or res[1].C % 8 == 0)))
-        narrow = cin_tot <= 64 and cres <= 64 and Cout <= (16 if stride == 2 else (8 if up2 else 32))
-        wide = rp and not narrow
-        stripe = False
-        if rp:
-            cfg = 6                      # 8 x 64 tiles
-            if Ho * Wo <= 64 * 64 and (Wo <= 32 or Cout <= 8):
-                cfg = 7                  # measured: 8x32 tiles for 8-channel layers at <= 64^2 (twice the workgroups) and for images no
-                                         # wider than a tile; 16 output channels at 64^2 stay on 8x64 (B fragments staged per workgroup)
-            if Cout > 16:
-                cfg = 7                  # four N tiles are only instantiated for the 8x32 tile
-            if up2:
-                cfg = 6                  # the up- / down-sampling members have one tile shape each
-            if stride == 2 or wide:
-                cfg = 7
-            if wide and stride == 1 and not up2 and Wo % 64 == 0 and Cout >= 32 and not ws.half:
-                cfg = 6                  # 8 x 64 tiles for the wide k3 s1 convs
-            if wide and stride == 1 and not up2 and Wo <= 16 and Ho > 8 and Cout >= 32 and not ws.half:
-                cfg = 10                 # 16 x 16 tiles for images no wider than 16
-            gemm = wide and ksize == 3 and stride == 1 and (not up2 or res is None) and not ws.half and cin_tot % 32 == 0 and cres % 32 == 0 and Cout % 64 == 0 \
-                and id(wpack) in pk.conv_ig and (cres == 0 or id(res[2]) in pk.conv_ig)
-            if gemm:
-                cfg = 11                 # the wide GEMM kernel (conv_wide.hip): 8 x 16 pixels x 128 (or 64) channels per workgroup
-            th, tw = {6: (8, 64), 7: (8, 32), 10: (16, 16), 11: (8, 16)}[cfg]
-            nt = -(-Ho // th) * -(-Wo // tw)
-            cls = "L" if Ho * Wo > 128 * 128 else ("M" if Ho * Wo > 64 * 64 else "S")
-            if narrow and ((ksize == 3 and stride == 1) or (ksize == 4 and stride == 2)) and not ws.half and cls in CONV_STRIPE:
-                rows = self._stripe_rows(batch, Ho, Wo, in0, in1, Cout, gn, res, up2, ksize, stride)
-                if rows:
-                    cfg, nt, stripe = 12, Ho // rows, True
-        if ws.store16 and (not rp or wide):
+        r0, r1, rw, rb = res if res is not None else (None,) * 4
+        srcs = [a for a in (in0, in1) if a is not None]
+        rsrcs = [a for a in (r0, r1) if a is not None and rw is not None]        # inputs of the 1x1 residual conv
+        batch = ws.B2 if (conditioned or any(a.batch == ws.B2 for a in (in0, in1, r0, r1) if a is not None)) else ws.B
+        cin_tot, cres = sum(a.C for a in srcs), sum(a.C for a in rsrcs)
+        rt = R.route(_conv_knobs(), batch=batch, H=Ho, W=Wo, cin=cin_tot, cres=cres, cout=Cout, ksize=ksize, stride=stride, up2=bool(up2),
+                     octets=all(a.C % 8 == 0 for a in srcs + rsrcs), has_res=res is not None,
+                     frag_rp=id(wpack) in pk.conv_rp and (rw is None or id(rw) in pk.conv_rp),
+                     frag_ig=id(wpack) in pk.conv_ig and (rw is None or id(rw) in pk.conv_ig),
+                     half=ws.half, pipelined=ws.pipelined, sr=self.unet.lowres_cond, producer_rev=in0.rev,
+                     stripe_rows=lambda: self._stripe_rows(batch, Ho, Wo, in0, in1, Cout, gn, res, up2, ksize, stride))
+        if ws.store16 and rt.family not in (R.NARROW, R.STRIPE):
             raise _Store16Unsupported()          # only the narrow row-paired kernels read bf16 activations
-        out = self._new_act(ws, batch, Cout, Ho, Wo, nt if want_stats else 0, fp32=out_fp32)
+        out = self._new_act(ws, batch, Cout, Ho, Wo, rt.tiles if want_stats else 0, fp32=out_fp32)
+        out.rev = rt.reverse
         p = L.MiConvParams()
         p.B, p.H, p.W = batch, Ho, Wo
         p.in0 = in0.c(batch)
@@ -550,55 +513,31 @@ class UnetEngine:
             p.gn_groups, p.gn_gamma, p.gn_beta, p.gn_eps = gn.num_groups, L.ptr(gn.weight), L.ptr(gn.bias), gn.eps
             if ss_off is not None:
                 p.scale_shift, p.ss_stride, p.ss_off = L.ptr(ws.ss), ws.ss.shape[1], ss_off
-        if res is not None:
-            r0, r1, rw, rb = res
+        if r0 is not None:
             p.res0 = r0.c(batch)
             if r1 is not None:
                 p.res1 = r1.c(batch, skip_scale)
             p.res_w, p.res_b = L.ptr(rw), L.ptr(rb)
         p.out_st = out.st
-        p.out, p.out_stats, p.tile_cfg = L.ptr(out.t), L.ptr(out.stats), cfg | 0x100 | (0x400 if ws.half else 0) | (0x800 if (CONV_SPLIT8 and Ho * Wo <= CONV_SPLIT8 * CONV_SPLIT8) else 0)
-        if wide:
+        p.out, p.out_stats, p.tile_cfg = L.ptr(out.t), L.ptr(out.stats), rt.word
+        if rt.rp:
+            frags = pk.conv_ig if rt.gemm else pk.conv_rp
+            frag, p.w_rp_exp = frags[id(wpack)]
+            p.w_rp = L.ptr(frag)
+            if rw is not None:
+                rfrag, p.res_w_rp_exp = frags[id(rw)]
+                p.res_w_rp = L.ptr(rfrag)
+        if rt.wide:
             coef = torch.zeros(batch, cin_tot, 4, dtype=torch.float32, device=ws.dev)
             exps = torch.zeros(batch, 2, dtype=torch.int32, device=ws.dev)
             ws.tensors += [coef, exps]
             p.gn_coef, p.gn_exps = L.ptr(coef), L.ptr(exps)
-        if rp:
-            # the consumer walks the image groups in the opposite order of its producer: what was written last (still in the memory-side
-            # cache / L2) is read first (speed only; measured -1.2 % on the SR step)
-            out.rev = bool(CONV_REVERSE) and batch % 8 == 0 and not in0.rev
-            if out.rev:
-                p.tile_cfg |= 0x200
-            cls = "L" if Ho * Wo > 128 * 128 else ("M" if Ho * Wo > 64 * 64 else "S")
-            nt_knob = RP_NTILE_BY[cls] or RP_NTILE
-            if not nt_knob and ws.pipelined and RP_NTILE_PIPE[cls] and batch * nt // RP_NTILE_PIPE[cls] >= 256:
-                nt_knob = RP_NTILE_PIPE[cls]        # (only while the launch still has a workgroup per CU: smaller batches keep the library's choice -- config 3 at B = 16: 39.1 K with, 40.7 K without)
-            if stripe:
-                nt_knob = self._stripe_nblk(ws, cls, nt, batch)
-            p.tile_cfg |= (nt_knob & 0xf) << 12
-            frags = pk.conv_ig if gemm else pk.conv_rp
-            frag, p.w_rp_exp = frags[id(wpack)]
-            p.w_rp = L.ptr(frag)
-            if res is not None and res[2] is not None:
-                rfrag, p.res_w_rp_exp = frags[id(res[2])]
-                p.res_w_rp = L.ptr(rfrag)
-        if wide:
             ws.prog.append((lib.mi_gn_coef_fwd, p, "gn_coef"))
-            if gemm:
-                ws.ig_convs.append((p, lib.mi_conv_prep_bytes(batch, cin_tot, cres, Ho, Wo)))
-                ws.prog.append((lib.mi_conv_prep_fwd, p, "conv_prep"))
+        if rt.gemm:
+            ws.ig_convs.append((p, lib.mi_conv_prep_bytes(batch, cin_tot, cres, Ho, Wo)))
+            ws.prog.append((lib.mi_conv_prep_fwd, p, "conv_prep"))
         ws.prog.append((lib.mi_conv_fwd, p, "conv"))
         return out
-
-    def _stripe_nblk(self, ws, cls, nt, batch) -> int:
-        """statistics blocks per workgroup of the stripe kernel (must divide the blocks of an image; 0 = the library's choice)"""
-        nt_knob = ST_NBLK[cls]
-        if ws.pipelined and ST_NBLK_PIPE[cls] and nt % ST_NBLK_PIPE[cls] == 0 and batch * nt // ST_NBLK_PIPE[cls] >= 128 \
-                and self.unet.lowres_cond:       # (super-resolution U-Nets only: on the base U-Net it costs the base stage 7 %: 97.1 against 104.8 K steps/s, and gives the cascade nothing)
-            nt_knob = ST_NBLK_PIPE[cls]
-        if nt_knob and (nt % nt_knob or nt_knob > 15):
-            nt_knob = 0
-        return nt_knob
 
     # ------------------------------------------------------------------ guidance fold (DESIGN section 21)
     def _cfg_fold_rows(self, ws, rb: ResnetBlock, x: Act) -> int:
@@ -607,9 +546,8 @@ class UnetEngine:
         if not CFG_FOLD or ws.no_fold or ws.B2 != 2 * ws.B or ws.half or u.init_conv_to_final_conv_residual or rb.cross_attn is not None \
                 or isinstance(rb.res_conv, nn.Conv2d) or x.batch != ws.B2 or (CFG_FOLD < 2 and x.H * x.W <= 128 * 128):
             return 0
-        cls = "L" if x.H * x.W > 128 * 128 else ("M" if x.H * x.W > 64 * 64 else "S")
         Cout = rb.block2.project.out_channels
-        if not CONV_RP or cls not in CONV_STRIPE or Cout != rb.block2.project.in_channels or Cout != x.C:
+        if not CONV_RP or R.size_class(x.H, x.W) not in CONV_STRIPE or Cout != rb.block2.project.in_channels or Cout != x.C:
             return 0
         half = x.rows(0, ws.B)
         return self._stripe_rows(ws.B, x.H, x.W, half, half, Cout, SimpleNamespace(num_groups=2 * rb.block2.groupnorm.num_groups), (half, half, None, None))
@@ -636,11 +574,10 @@ class UnetEngine:
         if ss_off is not None:                        # in0 = the null rows [B, 2B) of the step's table, in1 = the conditional rows B above them
             p.scale_shift, p.ss_stride, p.ss_off, p.ss_row1 = L.ptr(ws.ss[B:]), ws.ss.shape[1], ss_off, -B
         p.res0, p.res1 = x.rows(B, B).c(B), x.rows(0, B).c(B)
-        cls = "L" if H * W > 128 * 128 else ("M" if H * W > 64 * 64 else "S")
-        p.out, p.out_stats, p.tile_cfg = L.ptr(out.t), L.ptr(out.stats), 12 | 0x100 | ((self._stripe_nblk(ws, cls, nt, B) & 0xf) << 12)
-        out.rev = bool(CONV_REVERSE) and B % 8 == 0 and not h.rev
-        if out.rev:
-            p.tile_cfg |= 0x200
+        k = _conv_knobs()
+        out.rev = R.reverse_order(k, B, h.rev)
+        strips = R.stripe_strips(k, R.size_class(H, W), nt, B, ws.pipelined, self.unet.lowres_cond)
+        p.out, p.out_stats, p.tile_cfg = L.ptr(out.t), L.ptr(out.stats), R.tile_word(R.TILE_STRIPE, reverse=out.rev, strips=strips)
         ws.cfg_fold = SimpleNamespace(p=p, conv=conv, scale=None)
         self.set_guidance(ws, 1.0)                    # a fresh workspace is runnable: [0 ; W2] reproduces the conditional prediction
         ws.prog.append((lib.mi_conv_fwd, p, "conv"))
@@ -838,10 +775,7 @@ class UnetEngine:
         ws.tensors += [xh, gv]
         xa = x.c(batch)
         ws.tensors.append(xa)
-
-        def ln_call(_p, st, xa=xa, xh=xh):
-            return lib.mi_ln_tokens_fwd(C.byref(xa), batch, HW, L.ptr(at.norm.gamma), L.ptr(at.norm.beta), L.ptr(xh), st)
-        ws.prog.append((lambda p_, st: ln_call(p_, st), None, "ln_tokens"))
+        ws.prog.append(self._call(lib.mi_ln_tokens_fwd, "ln_tokens", C.byref(xa), batch, HW, L.ptr(at.norm.gamma), L.ptr(at.norm.beta), L.ptr(xh)))
         mg, mv, g0, v0 = pk.attn[id(at)]
         fp = L.MiAttnFoldParams()
         fp.B2, fp.C, fp.cd, fp.heads, fp.JT = batch, Cc, Cc, at.heads, jt
@@ -944,15 +878,14 @@ class UnetEngine:
         # (ws.prog_pre, see prepare_lowres) and is added back by the per-step kernel.
         cin = u.init_conv.convs[0].in_channels
         assert cin == u.channels * (2 if u.lowres_cond else 1)
-        cfg, nt = self._tile_cfg(H, W, B)
         ce_mfma = bool(pk.ce_mfma) and W % 4 == 0
         if ws.store16 and not ce_mfma:
             raise _Store16Unsupported()
         if ce_mfma:                       # its own tile shapes: 32 x 64 for large images, 16 x 32 below (enough workgroups at 64 x 64)
             cfg = 8 if H * W >= 128 * 128 else 9
-            th, tw = C.c_int(), C.c_int()
-            lib.mi_conv_tile_shape(cfg, C.byref(th), C.byref(tw))
-            nt = -(-H // th.value) * -(-W // tw.value)
+        else:
+            cfg = R.direct_code(H, W)
+        nt = R.tile_count(cfg, H, W)
         ctot = sum(u.init_conv.dim_scales)
         if len(u.init_conv.convs) > 3:
             raise NotImplementedError("CrossEmbedLayer with more than 3 kernel sizes")
@@ -973,7 +906,7 @@ class UnetEngine:
             ce.out_st = 1 if ws.store16 else 0
             if ce_mfma:
                 tab, exps = pk.ce_mfma[chan0]
-                ce.w_mfma, ce.tile_cfg = L.ptr(tab), cfg | (0x400 if ws.half else 0)
+                ce.w_mfma, ce.tile_cfg = L.ptr(tab), cfg | (R.MI_CONV_HALF if ws.half else 0)
                 for i in range(3):
                     ce.w_mfma_exp[i] = exps[i]
             return ce
@@ -1218,17 +1151,17 @@ class UnetEngine:
     def run_step(self, ws, stream=None, t_off: int = 0):
         """One denoising step's U-Net evaluation inside the sampling loop: scatter the current step's conditioning (see
         prepare_step_tables), then the image kernels."""
-        st = L.current_stream() if stream is None else stream
-        for fn, p, name in self.stage_prog(ws, t_off) + ws.prog:
-            rc = fn(C.byref(p), st) if p is not None else fn(None, st)
-            if rc != 0:
-                L.check(rc, name)
+        self._replay(self.stage_prog(ws, t_off) + ws.prog, stream)
 
     def run(self, ws, stream=None):
         """Enqueue one U-Net evaluation (all conditioning rows) on the current stream: ws.x / ws.times /
         ws.lowres / ws.lowres_times -> ws.pred."""
+        self._replay(ws.prog_cond + ws.prog, stream)
+
+    @staticmethod
+    def _replay(prog, stream=None):
         st = L.current_stream() if stream is None else stream
-        for fn, p, name in ws.prog_cond + ws.prog:
+        for fn, p, name in prog:
             rc = fn(C.byref(p), st) if p is not None else fn(None, st)
             if rc != 0:
                 L.check(rc, name)

@@ -37,6 +37,16 @@ def test_struct_layouts_match_the_library():
     L.use_library(L.DEFAULT_LIB)    # _bind() compares sizeof() of every parameter struct
 
 
+def test_conv_route_flag_bits_match_the_header():
+    """the named tile_cfg bits of the conv launch policy are the header's #defines"""
+    from minimagen_amd import conv_route
+    hdr = open(os.path.join(ROOT, "include", "minimagen_hip.h")).read()
+    for name in ("MI_CONV_SPLIT16", "MI_CONV_REVERSE", "MI_CONV_HALF", "MI_CONV_SPLIT8"):
+        m = re.search(rf"#define {name}\s+(0x[0-9a-fA-F]+)", hdr)
+        assert m, f"{name} is no longer defined in minimagen_hip.h"
+        assert getattr(conv_route, name) == int(m.group(1), 16), name
+
+
 def test_integration_md_binding_example_matches_the_abi():
     """INTEGRATION.md shows the ctypes binding a maintainer would write: the struct it spells out must have the library's layout (a
     binder copying the document must pass mi_struct_size) and the ABI version it quotes must be the header's"""

@@ -169,6 +169,24 @@ def test_reversed_image_order_of_alternate_convs_is_bit_exact(backend, monkeypat
     assert (outs[0] - ref).abs().max() < FWD_ATOL * max(1.0, ref.abs().max().item())
 
 
+@pytest.mark.emu
+def test_launch_plans_match_the_recorded_snapshot():
+    """every launch of the plans UnetEngine.workspace() builds (tools/dump_conv_plans.py: both golden U-Nets and two wide ones over batch
+    sizes, resolutions, precisions and knob settings that reach every conv family and tile code) is, field for field, the one recorded in
+    tests/golden/conv_plans.txt.gz (the tool's text output, 0.65 MB, gzipped): which kernel, tile, flags and buffers a launch gets does not
+    move unless the snapshot is re-recorded"""
+    import gzip
+    import os
+    from tools import dump_conv_plans
+    setup("emu")
+    want = gzip.open(os.path.join(I.GOLDEN, "conv_plans.txt.gz"), "rt").read().splitlines()
+    got = dump_conv_plans.dump()
+    assert sum(1 for ln in got if ln.startswith("#")) >= 40
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g == w, f"line {k + 1} (plan {[ln for ln in got[:k + 1] if ln.startswith('#')][-1]})"
+    assert len(got) == len(want)
+
+
 def _fp64_oracle(sd, x, tm, **kw):
     """the oracle's algorithm evaluated in fp64 (oracle/restated.py COMPUTE_DTYPE): the exact value fp32 implementations scatter around"""
     sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
