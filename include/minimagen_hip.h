@@ -66,6 +66,18 @@ typedef struct mi_act {
  *              or res0.scale*res0 + res1.scale*res1 (two Cout-channel tensors, no res_w: the guidance fold, tile_cfg 12)
  * Weights are pre-packed by the host: w[Cin][k][k][Cout_pad], Cout_pad = Cout rounded up to cout_tile.
  * The epilogue also emits the per-channel partial stats of `out` when out_stats != NULL.
+ *
+ * Domain of the row-paired matrix-core path (w_rp != NULL) for an input WITHOUT GroupNorm (gn_groups == 0, in0.stats given: the plain
+ * convs and, in training, the data-gradient conv over a loss gradient): every image is scaled by 2^ka, ka = clamp(4 - e(m), -60, 60)
+ * with m = 4 * rms of the image over all its channels and m in [2^(e-1), 2^e), so that 4 * rms lands in [8, 16) before the fp16 hi|lo
+ * split.  The scaling is a power of two, hence exact: the relative accuracy (2e-5 of the image's largest output, the family's gate) is
+ * the same for every per-image rms in
+ *       [2^-59, 2^62)  ~  [1.7e-18, 4.6e18),
+ * the range in which the clamp is not reached -- per image: images of one launch may lie anywhere in it, 18 decades apart.  Below it the
+ * exponent stays at +60 and the lo half's absolute step 2^-25 grows against the shrinking image: 2e-6 of the image at rms 1e-20, 1.6e-4
+ * at 1e-22; below rms 2^-75 ~ 2.6e-23 the mean square rounds to zero in fp32, no scaling is applied and the output is all zeros.  Above
+ * it the exponent stays at -60 and an element of 65504 * 2^60 ~ 7.5e22 or more becomes inf.  An all-zero image gives exact zeros.  The
+ * direct-conv family (w_rp == NULL) multiplies in fp32 and has fp32's own range.  (tests/test_block_bwd_ops.py)
  */
 typedef struct mi_conv_params {
     int B, H, W;            /* OUTPUT height/width */
