@@ -858,6 +858,31 @@ int mi_cfg_rescale_chunks(int n);   /* ceil(n / MI_CFG_RESCALE_CHUNK) */
 int mi_cfg_rescale_stats_fwd(const mi_cfg_rescale_params* p, void* stream);
 int mi_cfg_rescale_apply_fwd(const mi_cfg_rescale_params* p, void* stream);
 
+/* ---- guidance schedules: the guidance scale per step and per row, read from device memory -------------------------------------
+ * scale_tab is fp32 [S][B]; row k belongs to the step whose device-resident index *t_state is k (the row order of the sampler's coefficient
+ * table: row S - 1 is the first step executed).  Every entry reads s = scale_tab[(*t_state - t_off) * B + b] for image b, so a captured
+ * graph serves every step of a run and every later call's values.  The caller keeps 0 <= *t_state - t_off < S, as for the coefficient table.
+ *   mi_cfg_sched_combine_fwd          pred2[b] <- s == 1 ? c : u + (c - u) * s  (the three roundings above; a row at scale 1 keeps c to the
+ *                                     bit).  Rows [B, 2B) are not written.  `rescale` and `partials` are not used (rescale is still checked).
+ *   mi_cfg_sched_rescale_stats_fwd /  mi_cfg_rescale_stats_fwd / mi_cfg_rescale_apply_fwd with the scale read from the table: the same chunking,
+ *   mi_cfg_sched_rescale_apply_fwd    fp64 tree and fail-stop NaN behaviour; a constant table gives the bits of the scalar entries.
+ * Grid (mi_cfg_rescale_chunks(n), B), 256 work-items, 16-byte accesses when n % 4 == 0 and pred2 is 16-byte aligned.
+ * MI_ERR_INVALID (nothing is launched): B or n not positive, B > 65535, n > 2^30, NULL pred2 / scale_tab / t_state, negative t_off, rescale
+ * outside [0, 1], NULL partials for the two rescale entries.
+ * Struct index 34 of mi_struct_size; added within ABI 12 (no existing entry changed). */
+typedef struct mi_cfg_sched_params {
+    int B, n;
+    float* pred2;                   /* [2B][n], as in mi_cfg_rescale_params */
+    const float* scale_tab;         /* [S][B] fp32, device */
+    const int* t_state;             /* device-resident step index */
+    int t_off;                      /* the step is *t_state - t_off (the steps of one captured graph share one advance) */
+    float rescale;
+    double* partials;               /* [B][mi_cfg_rescale_chunks(n)][4] for the rescale entries, else NULL */
+} mi_cfg_sched_params;
+int mi_cfg_sched_combine_fwd(const mi_cfg_sched_params* p, void* stream);
+int mi_cfg_sched_rescale_stats_fwd(const mi_cfg_sched_params* p, void* stream);
+int mi_cfg_sched_rescale_apply_fwd(const mi_cfg_sched_params* p, void* stream);
+
 /* ---- HIP graphs: capture a sequence of the calls above once, replay it per timestep ------- */
 int mi_graph_begin(void* stream);
 int mi_graph_end(void* stream, void** graph_exec);

@@ -292,8 +292,9 @@ class Imagen(nn.Module):
         return start, stop, inpaint, start_image
 
     def _parse_guidance(self, batch_size: int, cond_scale, texts, text_embeds, text_masks, negative_texts, negative_text_embeds,
-                        negative_text_masks, guidance_rescale):
-        """-> (phi: 0. when off, negative captions: None, a list of ``batch_size`` strings, or (embeds, mask or None) still where the caller has
+                        negative_text_masks, guidance_rescale, guided: bool = None):
+        """``guided``: whether any step of the call is guided (None: ``cond_scale`` != 1, a call without a guidance schedule).
+        -> (phi: 0. when off, negative captions: None, a list of ``batch_size`` strings, or (embeds, mask or None) still where the caller has
         them).  Host only; raises ValueError on bad or inconsistent values."""
         phi = 0.
         if guidance_rescale is not None:
@@ -333,9 +334,60 @@ class Imagen(nn.Module):
                 raise ValueError(f"negative prompts: unmasked captions of different lengths ({text_embeds.shape[1]} and {e.shape[1]}) cannot be "
                                  "joined; pass masks")
             negative = (e.detach(), None if m is None else m.detach())
-        if (phi or negative is not None) and cond_scale == 1.:
-            raise ValueError("negative prompts and guidance_rescale need cond_scale != 1: at 1 the second half of the guidance batch is never evaluated")
+        if (phi or negative is not None) and not (cond_scale != 1. if guided is None else guided):
+            raise ValueError("negative prompts and guidance_rescale need cond_scale != 1 (or a guidance schedule with a guided step): at 1 the second "
+                             "half of the guidance batch is never evaluated")
         return phi, negative
+
+    def _parse_guidance_schedule(self, batch_size: int, cond_scale, solvers, guidance_interval, guidance_schedule):
+        """-> None when neither keyword is given, else per stage None (``cond_scale`` on every step, the call as it was) or that stage's guidance
+        scales, float64 [S] or [S, B] in execution order (sampler.guidance_scale_table).  Host only; raises ValueError on bad values."""
+        if guidance_interval is None and guidance_schedule is None:
+            return None
+        n_stages = len(self.unets)
+
+        def per_stage(v, name, single):
+            if single(v):
+                return [v] * n_stages
+            if not isinstance(v, (list, tuple)) or len(v) != n_stages:
+                raise ValueError(f"{name} needs one entry per stage ({n_stages})")
+            return list(v)
+
+        def number(v):
+            return not isinstance(v, bool) and isinstance(v, (int, float))
+
+        intervals = [None] * n_stages
+        if guidance_interval is not None:
+            is_pair = lambda v: isinstance(v, (list, tuple)) and len(v) == 2 and all(number(x) for x in v)
+            intervals = per_stage(guidance_interval, "guidance_interval", is_pair)
+            for iv in intervals:
+                if iv is None:
+                    continue
+                if not is_pair(iv) or not 0. <= float(iv[0]) <= float(iv[1]) <= 1.:
+                    raise ValueError(f"guidance_interval must be (lo, hi) with 0 <= lo <= hi <= 1 (or None for a stage), got {iv!r}")
+            if all(iv is None for iv in intervals):
+                raise ValueError("guidance_interval: every stage's entry is None")
+            intervals = [None if iv is None else (float(iv[0]), float(iv[1])) for iv in intervals]
+        schedules = [None] * n_stages
+        if guidance_schedule is not None:
+            if cond_scale != 1.:
+                raise ValueError("guidance_schedule is the scale itself: leave cond_scale at 1")
+            schedules = per_stage(guidance_schedule, "guidance_schedule", callable)
+            if all(s is None for s in schedules):
+                raise ValueError("guidance_schedule: every stage's entry is None")
+        elif cond_scale == 1.:
+            raise ValueError("guidance_interval needs cond_scale != 1 (or a guidance_schedule): outside the interval the scale is 1 already")
+        if isinstance(cond_scale, bool) or not isinstance(cond_scale, (int, float)) or cond_scale != cond_scale or abs(cond_scale) == float("inf"):
+            raise ValueError(f"cond_scale must be a finite number, got {cond_scale!r}")
+        tables = []
+        for stage, sched in enumerate(self.noise_schedulers):
+            if intervals[stage] is None and schedules[stage] is None:
+                tables.append(None)
+                continue
+            T = sched.num_timesteps
+            tau = torch.arange(T) if solvers[stage] is None else sched.sampling_timestep_map(solvers[stage][0])
+            tables.append(S.guidance_scale_table(tau, T, batch_size, cond_scale, intervals[stage], schedules[stage]))
+        return tables
 
     def _lowres_conditioning(self, unet: Unet, img, image_size: int, ws, lowres_noise_level: float, noise_fn, seed, sample0, stage):
         """Imagen.py:479-485 + :393: cubic resize (reflect pad) -> q_sample at int(T*level) -> *2-1."""
@@ -367,7 +419,7 @@ class Imagen(nn.Module):
                inpaint_images: torch.Tensor = None, inpaint_masks: torch.Tensor = None, start_image: torch.Tensor = None,
                start_at_stage: int = None, stop_at_stage: int = None,
                negative_texts: Union[str, List[str]] = None, negative_text_embeds: torch.Tensor = None, negative_text_masks: torch.Tensor = None,
-               guidance_rescale: float = None):
+               guidance_rescale: float = None, guidance_interval=None, guidance_schedule=None):
         """minimagen/Imagen.py:424-510.  Private keyword-only extras (not in the reference): ``_noise(shape)`` injects a
         host noise stream in the reference's draw order (parity runs); otherwise noise is Philox keyed by
         (``_seed``, ``_sample_offset`` + row, stage, step, element) so a sharded batch reproduces the unsharded one;
@@ -405,15 +457,30 @@ class Imagen(nn.Module):
         deviation of the conditional prediction c and mixed with itself, g * (phi * std(c) / std(g) + 1 - phi), on what the U-Net predicts
         (whatever its objective), before x0 and the dynamic threshold.  Both go with every setting above.  Bad values raise ValueError
         before anything is launched; a call with neither goes through exactly the workspaces, states, graphs and kernels it went through
-        before they existed.  Nothing here has been tried on a trained model: what is checked is the arithmetic."""
+        before they existed.  Nothing here has been tried on a trained model: what is checked is the arithmetic.
+
+        Guidance over the steps (keyword-only, not in the reference).  ``guidance_interval`` = (lo, hi), 0 <= lo <= hi <= 1,
+        one pair for every stage or a list with a pair or None per stage (needs ``cond_scale`` != 1 or a schedule): the step at trained
+        timestep tau is guided with ``cond_scale`` iff lo (T - 1) <= tau <= hi (T - 1) (Kynkaanniemi et al. 2024); every other step runs
+        unguided, over B rows of the U-Net instead of 2 B.  ``guidance_schedule`` IS the scale per step (``cond_scale`` stays 1): a callable
+        f(u) -> float of u = tau / (T - 1) for every stage, or a list with one entry per stage -- None, a callable, or a float tensor /
+        sequence [S] or [S, B] (per row), entry 0 the first step executed (the noisiest).  With both, steps outside the interval get scale 1.
+        A step whose scales are all exactly 1 is unguided (negative prompts and ``guidance_rescale``, the identity there, are skipped; they
+        need one guided step somewhere).  A stage moves between its B-row and its 2 B-row workspace at the run boundaries (x, the
+        dpmpp_2m history and the step index are handed over; same noise stream); an interval of (0, 1), a constant schedule s or an
+        all-ones schedule IS the call with ``cond_scale`` = s / 1.  Bad values, lengths and shapes raise ValueError before anything is launched."""
         solvers = self._parse_solver(sample_steps, sampler, sampler_eta)
-        rescale, negative = 0., None
+        rescale, negative, scale_tabs = 0., None, None
         if exists(text_embeds) or exists(texts):
-            first_stage, end_stage, inpaint, start_image = self._parse_inpaint(text_embeds.shape[0] if exists(text_embeds) else len(texts), inpaint_images,
-                                                                               inpaint_masks, start_image, start_at_stage, stop_at_stage)
-            rescale, negative = self._parse_guidance(text_embeds.shape[0] if exists(text_embeds) else len(texts), cond_scale, texts, text_embeds, text_masks,
-                                                     negative_texts, negative_text_embeds, negative_text_masks, guidance_rescale)
-        call_args = dict(negative_texts=negative_texts, negative_text_embeds=negative_text_embeds, negative_text_masks=negative_text_masks,
+            n_rows = text_embeds.shape[0] if exists(text_embeds) else len(texts)
+            first_stage, end_stage, inpaint, start_image = self._parse_inpaint(n_rows, inpaint_images, inpaint_masks, start_image, start_at_stage, stop_at_stage)
+            scale_tabs = self._parse_guidance_schedule(n_rows, cond_scale, solvers, guidance_interval, guidance_schedule)
+            guided = None
+            if scale_tabs is not None:
+                guided = any(cond_scale != 1. if scale_tabs[s] is None else bool((scale_tabs[s] != 1.).any()) for s in range(first_stage, end_stage))
+            rescale, negative = self._parse_guidance(n_rows, cond_scale, texts, text_embeds, text_masks,
+                                                     negative_texts, negative_text_embeds, negative_text_masks, guidance_rescale, guided)
+        call_args = dict(guidance_interval=guidance_interval, guidance_schedule=guidance_schedule, negative_texts=negative_texts, negative_text_embeds=negative_text_embeds, negative_text_masks=negative_text_masks,
                          guidance_rescale=guidance_rescale, inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, start_image=start_image, start_at_stage=start_at_stage,
                          stop_at_stage=stop_at_stage, sample_steps=sample_steps, sampler=sampler, sampler_eta=sampler_eta, texts=texts, text_masks=text_masks, text_embeds=text_embeds, cond_scale=cond_scale, lowres_sample_noise_level=lowres_sample_noise_level,
                          return_pil_images=return_pil_images, device=device, _noise=_noise, _seed=_seed, _sample_offset=_sample_offset,
@@ -430,14 +497,21 @@ class Imagen(nn.Module):
             negative = t5_encode_text(negative, name=self.text_encoder_name)
         assert not (exists(text_embeds) and text_embeds.shape[-1] != self.text_embed_dim), \
             f'invalid text embedding dimension being passed in (should be {self.text_embed_dim})'
-        assert not (cond_scale != 1. and not self.can_classifier_guidance), \
+        # the runs of every stage's guidance plan, (kind, first step, one past the last, scale): ONE run over all steps for a call without
+        # a schedule or interval -- and for a table that is one row-uniform value on every step, which IS that call (sampler.guidance_plan)
+        plans = {}
+        for stage in range(first_stage, end_stage):
+            w_stage = None if scale_tabs is None else scale_tabs[stage]
+            n_steps = self.noise_schedulers[stage].num_timesteps if solvers[stage] is None else solvers[stage][0]
+            plans[stage] = [('plain' if cond_scale == 1. else 'scalar', 0, n_steps, cond_scale)] if w_stage is None else S.guidance_plan(w_stage)
+        any_guided = any(kind != 'plain' for runs in plans.values() for kind, *_ in runs)
+        assert not (any_guided and not self.can_classifier_guidance), \
             'imagen was not trained with conditional dropout, and thus one cannot use classifier free guidance (cond_scale anything other than 1)'
         batch_size = text_embeds.shape[0]
         device = next(self.parameters()).device
         lowres_sample_noise_level = default(lowres_sample_noise_level, self.lowres_sample_noise_level)
-        two = cond_scale != 1.
-        B2 = 2 * batch_size if two else batch_size
-        keep = torch.cat((torch.ones(batch_size, dtype=torch.bool), torch.zeros(B2 - batch_size, dtype=torch.bool)))
+        keeps = {kind: torch.cat((torch.ones(batch_size, dtype=torch.bool), torch.zeros(0 if kind == 'plain' else batch_size, dtype=torch.bool)))
+                 for kind in ('plain', 'scalar', 'table')}
         text_embeds = text_embeds.to(device)
         text_masks = text_masks.to(device) if exists(text_masks) else None
         if inpaint is not None:
@@ -502,8 +576,10 @@ class Imagen(nn.Module):
         # ... and neither does a noise-predicting stage: only another objective names itself (it selects the stage's coefficient table)
         extras = {stage: dict(known, **({} if self.pred_objectives[stage] == 'noise' else dict(objective=self.pred_objectives[stage])))
                   for stage, _ in stages}
-        # guidance rescale reads both halves of the prediction: a workspace of its own that never folds the guidance into the U-Net's tail
-        unfolded, rescaled = ({}, {}) if not rescale else (dict(fold=False), dict(rescale=rescale))
+        # guidance rescale reads both halves of the prediction: a workspace of its own that never folds the guidance into the U-Net's tail --
+        # and so does a run whose scales come from a table; an unguided run (B rows) takes neither, nor the negative captions
+        unfolded = {kind: dict(fold=False) if (kind == 'table' or (rescale and kind == 'scalar')) else {} for kind in keeps}
+        rescaled = {kind: dict(rescale=rescale) if (rescale and kind != 'plain') else {} for kind in keeps}
         # ---- pass 1, every stage on its own stream: what depends on the CAPTIONS only (text conditioning, the folded context rows, x_T, the
         # step tables) -- issued for all stages up front, so a later stage has it behind it when its low-resolution input arrives
         wss, begun = {}, {}
@@ -518,29 +594,40 @@ class Imagen(nn.Module):
                         t_in.record_stream(streams[stage])
             with (torch.cuda.stream(streams[stage]) if on_gpu else null_context()):
                 eng = unet.engine()
-                # per call, never sticky engine state: a later Unet.forward stays on the engine's default precision
-                ws = wss[stage] = eng.workspace(batch_size, B2, image_size, image_size, precision=precision, lane=lane,
-                                                pipelined=bool(_async and on_gpu and SAMPLE_LANES > 1), **unfolded)
-                eng.set_text(ws, text_embeds, text_masks, keep, **neg_text)
-                if unet.lowres_cond:             # the augmentation level's timestep feeds the step tables (diffusion_model.py:68-69)
-                    ws.lowres_times.fill_(int(self.lowres_noise_schedule.num_timesteps * lowres_sample_noise_level))
+                wss[stage] = {}
+                for kind in dict.fromkeys(run[0] for run in plans[stage]):          # every workspace the stage visits: its text, once per call
+                    # per call, never sticky engine state: a later Unet.forward stays on the engine's default precision
+                    ws = wss[stage][kind] = eng.workspace(batch_size, keeps[kind].numel(), image_size, image_size, precision=precision, lane=lane,
+                                                          pipelined=bool(_async and on_gpu and SAMPLE_LANES > 1), **unfolded[kind])
+                    eng.set_text(ws, text_embeds, text_masks, keeps[kind], **({} if kind == 'plain' else neg_text))
+                    if unet.lowres_cond:             # the augmentation level's timestep feeds the step tables (diffusion_model.py:68-69)
+                        ws.lowres_times.fill_(int(self.lowres_noise_schedule.num_timesteps * lowres_sample_noise_level))
                 if _noise is None:
                     begun[stage] = self._stage_begin(unet, (batch_size, self.channels, image_size, image_size), noise_scheduler=noise_scheduler,
-                                                     ws=ws, seed=_seed, sample0=_sample_offset, stage=stage, solver=solvers[stage], **extras[stage])
+                                                     ws=wss[stage][plans[stage][0][0]], seed=_seed, sample0=_sample_offset, stage=stage, solver=solvers[stage], **extras[stage])
         # ---- pass 2: the cascade
         img, prev_done = start_image, None
         for stage, (unet, channel, image_size, noise_scheduler) in stages:
             if on_gpu and prev_done is not None:
                 streams[stage].wait_event(prev_done)
             with (torch.cuda.stream(streams[stage]) if on_gpu else null_context()):
-                ws = wss[stage]
+                runs = plans[stage]
+                ws = wss[stage][runs[0][0]]
+                shape = (batch_size, self.channels, image_size, image_size)
                 if unet.lowres_cond:
                     if on_gpu:
                         img.record_stream(streams[stage])
                     self._lowres_conditioning(unet, img, image_size, ws, lowres_sample_noise_level, _noise, _seed, _sample_offset, stage)
-                img = self._p_sample_loop(unet, (batch_size, self.channels, image_size, image_size), noise_scheduler=noise_scheduler,
-                                          ws=ws, cond_scale=cond_scale, noise_fn=_noise, seed=_seed, sample0=_sample_offset,
-                                          stage=stage, use_graph=_use_graph, begun=begun.get(stage), solver=solvers[stage], **extras[stage], **rescaled)
+                    for other in wss[stage].values():           # drawn once, then copied
+                        if other is not ws:
+                            other.lowres.copy_(ws.lowres)
+                            unet.engine().prepare_lowres(other)
+                loop = dict(noise_scheduler=noise_scheduler, noise_fn=_noise, seed=_seed, sample0=_sample_offset, stage=stage, use_graph=_use_graph,
+                            solver=solvers[stage], **extras[stage])
+                if len(runs) == 1 and runs[0][0] != 'table':
+                    img = self._p_sample_loop(unet, shape, ws=ws, cond_scale=runs[0][3], begun=begun.get(stage), **loop, **rescaled[runs[0][0]])
+                else:
+                    img = self._run_plan(unet, shape, runs, wss[stage], scale_tabs[stage], begun.get(stage), loop, rescaled)
                 if on_gpu:
                     prev_done = streams[stage].record_event()
         pack_tokens = [] if (_noise is not None or _revalidated) else [(unet.engine(), unet.engine().pack_begin()) for unet in self.unets]
@@ -574,6 +661,29 @@ class Imagen(nn.Module):
         pil = _to_pil_images(img)
         self.check_device_status()
         return pil
+
+    def _run_plan(self, unet: Unet, shape, runs, workspaces, scales, begun, loop, rescaled):
+        """A stage whose guidance plan has several runs, or reads its scales from a table: every run on the workspace of
+        its kind, x / the history / the step index handed over at the run boundaries, one noise stream (``begun``: the stage_begin of the first
+        run's workspace, issued here for injected noise -- one x_T and one draw per step, whatever workspaces the stage visits) -> the image."""
+        first = workspaces[runs[0][0]]
+        begin = {k: loop[k] for k in ('noise_scheduler', 'stage', 'solver', 'inpaint', 'objective') if k in loop}
+        if begun is None:
+            begun = self._stage_begin(unet, shape, ws=first, noise_fn=loop['noise_fn'], seed=loop['seed'], sample0=loop['sample0'], **begin)
+        st0, noise_dev = begun
+        states = {runs[0][0]: st0}
+        for kind, ws in workspaces.items():
+            if ws is not first:
+                states[kind] = S.stage_attach(unet, shape, ws=ws, first=st0, max_states=MAX_SOLVER_STATES, **begin)
+        n_steps = runs[-1][2]
+        img = prev = None
+        for i, (kind, a, b, scale) in enumerate(runs):
+            if prev is not None:
+                S.stage_handover(states[prev], workspaces[prev], states[kind], workspaces[kind], shape[0], n_steps - 1 - a)
+            img = self._p_sample_loop(unet, shape, ws=workspaces[kind], cond_scale=1. if kind == 'table' else scale, begun=(states[kind], noise_dev),
+                                      steps=(a, b), scale_tab=scales if kind == 'table' else None, finalize=i == len(runs) - 1, **loop, **rescaled[kind])
+            prev = kind
+        return img
 
     def _poll_status(self, block: bool = False):
         """Status of the kernels whose workgroups wait for each other (the grouped sampler tail).  Such a launch is fail-stop: when a wait

@@ -237,6 +237,11 @@ class MiCfgRescaleParams(C.Structure):
     _fields_ = [("B", C.c_int), ("n", C.c_int), ("pred2", C.c_void_p), ("cond_scale", C.c_float), ("rescale", C.c_float), ("partials", C.c_void_p)]
 
 
+class MiCfgSchedParams(C.Structure):
+    _fields_ = [("B", C.c_int), ("n", C.c_int), ("pred2", C.c_void_p), ("scale_tab", C.c_void_p), ("t_state", C.c_void_p), ("t_off", C.c_int),
+                ("rescale", C.c_float), ("partials", C.c_void_p)]
+
+
 class MiPackConv3Desc(C.Structure):
     _fields_ = [("w", C.c_void_p), ("frag", C.c_void_p), ("generic", C.c_void_p), ("Cout", C.c_int), ("Cin", C.c_int), ("adjoint", C.c_int),
                 ("exp", C.c_int), ("cout_pad", C.c_int), ("reserved", C.c_int)]
@@ -246,7 +251,7 @@ _STRUCTS = {0: MiAct, 1: MiConvParams, 2: MiCrossEmbedParams, 3: MiLinear, 4: Mi
             6: MiAttnFoldParams, 7: MiCrossAttnParams, 8: MiCfgX0Params, 9: MiQuantileParams, 10: MiPosteriorParams,
             11: MiResizeParams, 12: MiSelfAttnParams, 13: MiChanFFParams, 14: MiFlashAttnParams, 15: MiTokensToNchwParams, 16: MiConvWgradParams, 17: MiBlockBwdParams, 18: MiCrossEmbedWgradParams, 19: MiFoldedAttnParams, 20: MiAdamTensor, 21: MiAdamParams, 22: MiPackConv3Desc,
             23: MiFlashAttnTrainParams, 24: MiSamplerExtParams, 25: MiInpaintParams, 26: MiInitDownParams, 27: MiAttnCondParams,
-            28: MiEmaTensor, 29: MiEmaParams, 31: MiDiffuseParams, 32: MiObjectiveLossParams, 33: MiCfgRescaleParams}
+            28: MiEmaTensor, 29: MiEmaParams, 31: MiDiffuseParams, 32: MiObjectiveLossParams, 33: MiCfgRescaleParams, 34: MiCfgSchedParams}
 
 _lib = None
 _backend = None
@@ -285,6 +290,9 @@ def _bind(lib):
     lib.mi_cfg_rescale_stats_fwd.argtypes = [vp, vp]
     lib.mi_cfg_rescale_apply_fwd.argtypes = [vp, vp]
     for name in ("mi_cfg_rescale_chunks", "mi_cfg_rescale_stats_fwd", "mi_cfg_rescale_apply_fwd"):
+        getattr(lib, name).restype = i32
+    for name in ("mi_cfg_sched_combine_fwd", "mi_cfg_sched_rescale_stats_fwd", "mi_cfg_sched_rescale_apply_fwd"):
+        getattr(lib, name).argtypes = [vp, vp]
         getattr(lib, name).restype = i32
     lib.mi_conv_prep_bytes.argtypes = [i32, i32, i32, i32, i32]
     lib.mi_conv_prep_bytes.restype = C.c_longlong

@@ -59,6 +59,7 @@ extern "C" int mi_struct_size(int which) {
         case 31: return (int)sizeof(mi_diffuse_params);             // (30 stays unassigned)
         case 32: return (int)sizeof(mi_objective_loss_params);
         case 33: return (int)sizeof(mi_cfg_rescale_params);
+        case 34: return (int)sizeof(mi_cfg_sched_params);
     }
     return -1;
 }

@@ -57,7 +57,8 @@ def sample_distributed(imagen, *, text_embeds: torch.Tensor, text_masks: Optiona
     ``inpaint_masks`` / ``start_image`` are passed full-batch as well and sharded by the same row bounds (the known-region draws are keyed
     like the step noise); ``start_at_stage`` / ``stop_at_stage`` go through (the gathered images then have the last stage's size that ran).
     ``negative_text_embeds`` / ``negative_text_masks`` (full batch) are sharded by the same bounds; ``guidance_rescale`` goes through (its
-    statistics are per image, so sharding changes no bit)."""
+    statistics are per image, so sharding changes no bit).  ``guidance_interval`` goes through; of a ``guidance_schedule`` (one entry per
+    stage) every [S, B] entry (per row, full batch) is sharded along dimension 1 by the same bounds, everything else goes through."""
     ws = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     batch = text_embeds.shape[0]
@@ -73,6 +74,14 @@ def sample_distributed(imagen, *, text_embeds: torch.Tensor, text_masks: Optiona
     for name in ("inpaint_images", "inpaint_masks", "start_image", "negative_text_embeds", "negative_text_masks"):
         if sample_kwargs.get(name) is not None:
             sample_kwargs[name] = sample_kwargs[name][lo:hi].contiguous()
+    schedule = sample_kwargs.get("guidance_schedule")
+    if isinstance(schedule, (list, tuple)):
+        def rows(entry):
+            if entry is None or callable(entry):
+                return entry
+            t = torch.as_tensor(entry)
+            return t[:, lo:hi].contiguous() if t.dim() == 2 else entry
+        sample_kwargs["guidance_schedule"] = [rows(entry) for entry in schedule]
     local = imagen.sample(text_embeds=text_embeds[lo:hi].contiguous(),
                           text_masks=None if text_masks is None else text_masks[lo:hi].contiguous(),
                           _sample_offset=seed_off + lo, **sample_kwargs)

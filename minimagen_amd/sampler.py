@@ -47,6 +47,68 @@ def cubic_resize(ws, img, image_size: int, stream):
     return up
 
 
+def guidance_scale_table(tau, T: int, B: int, cond_scale: float = 1., interval=None, schedule=None) -> torch.Tensor:
+    """A stage's guidance scales in EXECUTION order (entry 0: the first step executed, the noisiest one), float64 [S] or [S, B] (per row; the
+    caller's values as they are: a run at ONE scale is the call at that cond_scale, a table run rounds them to fp32).
+    ``tau`` int64 [S]: the trained timestep of step index k (GaussianDiffusion.sampling_timestep_map; arange(T) for the reference's loop) --
+    entry i is the step at tau[S - 1 - i].  ``schedule``: None (``cond_scale`` on every step), a callable f(u) -> float with
+    u = tau_k / (T - 1), or a tensor / sequence [S] or [S, B] already in execution order.  ``interval`` = (lo, hi): a step outside
+    lo (T - 1) <= tau_k <= hi (T - 1) (float64 against the integer tau_k) gets scale 1.  Host only; raises ValueError on bad values."""
+    taus = [int(v) for v in reversed(tau.tolist())]
+    S = len(taus)
+    if schedule is None:
+        w = torch.full((S,), float(cond_scale), dtype=torch.float64)
+    elif callable(schedule):
+        vals = []
+        for t in taus:
+            v = schedule(t / (T - 1))
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError(f"guidance_schedule: the callable must return a float, got {v!r}")
+            vals.append(float(v))
+        w = torch.tensor(vals, dtype=torch.float64)
+    else:
+        try:
+            w = torch.as_tensor(schedule).detach().to('cpu')
+        except Exception as e:
+            raise ValueError(f"guidance_schedule: not a tensor or a sequence of numbers ({e})")
+        if w.dtype == torch.bool or not (w.is_floating_point() or w.dtype in (torch.int32, torch.int64)):
+            raise ValueError(f"guidance_schedule: a float tensor or sequence, got dtype {w.dtype}")
+        w = w.to(torch.float64)
+        if w.dim() not in (1, 2) or w.shape[0] != S or (w.dim() == 2 and w.shape[1] != B):
+            raise ValueError(f"guidance_schedule: shape {tuple(w.shape)} is neither [{S}] (one scale per step executed) nor [{S}, {B}] (per row)")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("guidance_schedule: the scales must be finite")
+    if interval is not None:
+        lo, hi = interval
+        inside = torch.tensor([lo * (T - 1) <= t <= hi * (T - 1) for t in taus])
+        w = torch.where(inside if w.dim() == 1 else inside[:, None], w, torch.ones_like(w))
+    return w.contiguous()
+
+
+def guidance_plan(w: torch.Tensor):
+    """The runs of a stage whose guidance scales are ``w`` (float [S] or [S, B], execution order): a list of (kind, first step, one past the
+    last step, scale), maximal runs of steps of one kind --
+      'plain'   every row's scale is exactly 1: the B-row workspace, one U-Net row per image
+      'scalar'  ONE row-uniform scale s != 1 (all the stage's guided steps share it): the existing guided path at cond_scale = s, folded where
+                it folds today; ``scale`` = s
+      'table'   anything else: the unfolded 2B-row workspace, the scale read per step and row from device memory (``scale`` = None)
+    A single 'plain' or 'scalar' run over all S steps IS the existing call at cond_scale = 1 / s: same workspaces, states, graph keys, bits."""
+    w2 = w.reshape(w.shape[0], -1).to(torch.float64)
+    S = w2.shape[0]
+    guided = [bool((w2[i] != 1.).any()) for i in range(S)]
+    values = {float(v) for i in range(S) if guided[i] for v in w2[i].tolist()}
+    one = len(values) == 1                       # (a guided step with a row at 1 beside another value has two values: a table)
+    kind = lambda i: 'plain' if not guided[i] else ('scalar' if one else 'table')
+    runs, i = [], 0
+    while i < S:
+        j = i
+        while j < S and kind(j) == kind(i):
+            j += 1
+        runs.append((kind(i), i, j, 1. if kind(i) == 'plain' else (next(iter(values)) if one else None)))
+        i = j
+    return runs
+
+
 class StageState:
     """One stage's loop state, kept on its workspace (so it dies with the buffers it points into) per schedule -- or per (schedule, S,
     sampler, eta) for a call with ``solver`` = (S, sampler, eta).  Every field is a slot; ``ext`` and ``group_sync`` stay UNSET until they exist
@@ -55,13 +117,15 @@ class StageState:
     7, and the known-image / mask buffers every call copies into (so one captured graph serves every later call's images and masks);
     ``ip`` (None otherwise) is the kernels' block over them, rebuilt by every stage_begin.  ``objective`` (what the stage's U-Net predicts: 'noise',
     'x_start' or 'v') only chooses columns 0 and 1 of the coefficient table: no kernel, struct or launch knows about it.
-    ``rescale_partials`` (None until a call with guidance_rescale > 0 runs on this state): the [B][chunks][4] fp64 sums of mi_cfg_rescale_*."""
+    ``rescale_partials`` (None until a call with guidance_rescale > 0 runs on this state): the [B][chunks][4] fp64 sums of mi_cfg_rescale_*.
+    ``scale_tab`` (None until a 'table' run of a guidance schedule runs on this state): fp32 [S][B], row k the scales of step
+    index k, which every such call copies into -- the captured graphs address it, so they serve every later call's values."""
     __slots__ = ("coef", "tau", "t_map", "x0_prev", "ext", "t_state", "x0", "hist", "s_q", "v_q", "seed_dev", "graphs",
-                 "group_sync", "group_err_host", "group_failed", "group_heal", "known", "mask", "ip", "known_noise", "rescale_partials")
+                 "group_sync", "group_err_host", "group_failed", "group_heal", "known", "mask", "ip", "known_noise", "rescale_partials", "scale_tab", "scale_tab_host")
 
     def __init__(self, sched, B: int, n: int, dev, solver=None, hw: int = None, objective: str = 'noise'):
         self.tau = self.t_map = self.x0_prev = None     # the reference's loop has no step -> timestep map and no history
-        self.known = self.mask = self.ip = self.known_noise = self.rescale_partials = None
+        self.known = self.mask = self.ip = self.known_noise = self.rescale_partials = self.scale_tab = self.scale_tab_host = None
         known = {} if hw is None else dict(known=True)
         if objective != 'noise':
             known['objective'] = objective
@@ -171,6 +235,37 @@ def stage_begin(unet, shape, *, noise_scheduler, ws, noise_fn=None, seed: int = 
     return st, noise_dev
 
 
+def stage_attach(unet, shape, *, noise_scheduler, ws, first: StageState, stage: int = 0, solver=None, max_states: int = 8, inpaint=None,
+                 objective: str = 'noise') -> StageState:
+    """The state of a FURTHER workspace a stage visits in this call (a guidance plan of several runs), behind stage_begin on
+    the first one: its step tables, and for an inpainting call its known image and mask, copied from ``first`` (resized once) over the same
+    known-region noise.  No draw: x, the history and the step index arrive with the hand-over (stage_handover)."""
+    eng = unet.engine()
+    B, n = shape[0], shape[1] * shape[2] * shape[3]
+    T = noise_scheduler.num_timesteps if solver is None else solver[0]
+    st = stage_state(ws, noise_scheduler, B, n, solver, eng, max_states, hw=None if inpaint is None else shape[2] * shape[3], objective=objective)
+    if inpaint is not None:
+        st.known.copy_(first.known)
+        st.mask.copy_(first.mask)
+        st.known_noise = first.known_noise
+        st.ip = L.MiInpaintParams(L.ptr(st.known), L.ptr(st.mask), shape[2] * shape[3], (stage << 20) | (3 << 18), L.ptr(st.known_noise))
+    eng.prepare_step_tables(ws, T, st.t_state, L.current_stream(), t_map=st.tau)
+    return st
+
+
+def stage_handover(src: StageState, ws_src, dst: StageState, ws_dst, B: int, step: int):
+    """A run boundary on the stage's stream, outside the graphs: x (and the x0 history of dpmpp_2m) of the run that ended go to the next run's
+    workspace, whose device-resident step index becomes ``step`` -- the index the host knows.  Plain device copies."""
+    lib, stream = L.lib(), L.current_stream()
+    ws_dst.x.copy_(ws_src.x)
+    if dst.x0_prev is not None:
+        dst.x0_prev.copy_(src.x0_prev)
+    if dst.t_map is None:
+        L.check(lib.mi_step_set(L.ptr(dst.t_state), L.ptr(ws_dst.times), B, step, stream), "mi_step_set")
+    else:
+        L.check(lib.mi_step_set_mapped(L.ptr(dst.t_state), L.ptr(ws_dst.times), B, step, C.byref(dst.ext), stream), "mi_step_set_mapped")
+
+
 def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream):
     """What follows the U-Net evaluation in a step, fixed once per graph entry -> (launch, advance): ``launch(k)`` enqueues the tail kernels of
     step *t_state - k (``kind``: "small" one workgroup per image | "group" cooperating workgroups | "separate" kernels), ``advance(n)`` moves the
@@ -212,13 +307,18 @@ def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream):
 
 def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, noise_fn=None, seed: int = 0, sample0: int = 0,
                   stage: int = 0, use_graph: bool = True, begun=None, solver=None, group_max: int = 8, max_states: int = 8, inpaint=None,
-                  objective: str = 'noise', rescale: float = 0.):
+                  objective: str = 'noise', rescale: float = 0., steps=None, scale_tab=None, finalize: bool = True):
     """Imagen.py:373-420 + :329-370 + :261-326: T replays of [U-Net (both guidance halves) -> CFG combine + x0 -> dynamic-threshold quantile ->
     posterior draw -> t -= 1].  ``solver`` = (S, sampler, eta): S steps over a subsequence of the trained timesteps; the loop, the noise index and the
     Philox stream count STEPS: the reference's loop with T = S but for the state's step -> timestep map and history buffer (``st.ext``).
     ``objective``: what the U-Net predicts; it selects the stage state (its coefficient table) and nothing else.
     ``rescale`` = phi > 0 (guidance rescale; on a workspace built with fold=False): two launches between the U-Net and the tail
-    leave the rescaled guided prediction in rows [0, B) of ws.pred, and the tail runs as it does behind a folded U-Net."""
+    leave the rescaled guided prediction in rows [0, B) of ws.pred, and the tail runs as it does behind a folded U-Net.
+    One RUN of a guidance plan (DESIGN section 24): ``steps`` = (a, b) executes the steps a .. b - 1 of the T (counted from the first executed;
+    the state's step index is T - 1 - a on entry: stage_begin or stage_handover put it there) and, with ``finalize=False``, returns None
+    instead of the image.  ``scale_tab`` (host float [T] or [T, B] in execution order; on a workspace built with fold=False): the run reads its
+    scale per step and row from the state's ``scale_tab`` -- mi_cfg_sched_combine_fwd, or the sched forms of the two rescale launches,
+    between the U-Net and the tail."""
     lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
     B, Cc, H, W = shape
     n = Cc * H * W
@@ -227,11 +327,24 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
     eng.set_guidance(ws, cond_scale)
     rescale = float(rescale)
     assert not rescale or (two and ws.cfg_fold is None), "guidance rescale reads both halves of the prediction"
-    combine = two and ws.cfg_fold is None and not rescale        # guidance folded into the U-Net's tail / rescaled in place: ws.pred holds B guided rows
+    sched = scale_tab is not None
+    assert not sched or (two and ws.cfg_fold is None), "a table of guidance scales reads both halves of the prediction"
+    combine = two and ws.cfg_fold is None and not rescale and not sched   # guidance folded into the U-Net's tail / rescaled / combined in place: ws.pred holds B guided rows
     if begun is None:
         begun = stage_begin(unet, shape, noise_scheduler=noise_scheduler, ws=ws, noise_fn=noise_fn, seed=seed, sample0=sample0, stage=stage, solver=solver, max_states=max_states,
                             inpaint=inpaint, objective=objective)
     st, noise_dev = begun
+    a_step, b_step = (0, T) if steps is None else steps
+    assert 0 <= a_step < b_step <= T, steps
+    m_steps = b_step - a_step
+    if sched:                                # every call's values go into the buffer the captured launches address (row k: step index k)
+        if st.scale_tab is None:
+            st.scale_tab = torch.ones(T, B, dtype=torch.float32, device=ws.dev)
+        tab = torch.as_tensor(scale_tab, dtype=torch.float32).reshape(T, -1).expand(T, B).flip(0).contiguous()
+        # (a copy from pageable host memory blocks the host behind this stream: skipped when the values are the ones already there)
+        if st.scale_tab_host is None or not torch.equal(st.scale_tab_host, tab):
+            st.scale_tab.copy_(tab)
+            st.scale_tab_host = tab
     k_lo, k_hi, w = quantile_rank(n, im.dynamic_thresholding_percentile)
     # the whole tail in one launch: of one workgroup per image (n <= MI_SAMPLER_SMALL_N), or of <= group_max (0: never) cooperating workgroups -- but
     # for a stage state whose grouped launch ever failed (fail-stop: NaN images + the sticky error word, see Imagen._poll_status)
@@ -242,14 +355,60 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
     if st.group_heal:
         st.group_sync.zero_()               # stream-ordered behind every launch queued on this lane: ticket, counters, histograms, error word
         st.group_heal = False
-    # the captured graph of `per` steps is cached per (workspace, guidance, threshold, noise mode, shard offset, tail kind); the seed is in device memory
-    gkey = (float(cond_scale), two, k_lo, k_hi, w, sample0, stage, T, noise_dev is None, group) + (() if solver is None else (tuple(solver),)) + (() if st.ip is None else ("inpaint",)) + ((("rescale", rescale),) if rescale else ())
-    entry = st.graphs.get(gkey) if (use_graph and noise_dev is None) else None
     seed = int(seed) & 0x7FFFFFFFFFFFFFFF
     if noise_dev is None:
         if st.seed_dev is None:
             st.seed_dev = torch.zeros(1, dtype=torch.int64, device=ws.dev)
         st.seed_dev.fill_(seed)
+    # the captured graph of `per` steps is cached per (workspace, guidance, threshold, noise mode, shard offset, tail kind); the seed is in device memory
+    gkey = (float(cond_scale), two, k_lo, k_hi, w, sample0, stage, T, noise_dev is None, group) + (() if solver is None else (tuple(solver),)) + (() if st.ip is None else ("inpaint",)) + ((("rescale", rescale),) if rescale else ()) + (("sched",) if sched else ())
+    # `per` steps per captured graph (one replay boundary, ~9 us of idle GPU, per graph): step k addresses *t_state - k, one advance per graph
+    cap = int(os.environ.get("MINIMAGEN_STEPS_PER_GRAPH", "5"))
+    if m_steps == T:
+        per = next(k for k in (5, 4, 3, 2, 1) if k <= cap and T % k == 0)
+        lengths = [per] * (T // per)
+    else:                                    # a run of a plan: m // per graphs of per steps and one of m % per; such a graph's key carries its length
+        per = max(1, min(cap, 5, m_steps))
+        lengths = [per] * (m_steps // per) + ([m_steps % per] if m_steps % per else [])
+    keys = {length: gkey if m_steps == T else gkey + (("len", length),) for length in (lengths if use_graph else lengths[:1])}
+    if use_graph and noise_dev is None:
+        # bounded: one exec per (guidance, threshold, shard offset) combination and length; the oldest go, never one this run replays
+        missing = sum(1 for k in keys.values() if k not in st.graphs)
+        victims = [k for k in st.graphs if k not in keys.values()]
+        while missing and victims and len(st.graphs) + missing > 8:
+            destroy_graph(st.graphs.pop(victims.pop(0)), ws.dev)
+    entries = {}
+    for length, key in keys.items():
+        entries[length] = _loop_entry(im, unet, st, ws, key, length, B=B, n=n, T=T, two=two,
+                                      combine=combine, cond_scale=cond_scale, rescale=rescale, sched=sched, kind=kind, group=group, k_lo=k_lo,
+                                      k_hi=k_hi, w=w, noise_dev=noise_dev, seed=seed, sample0=sample0, stage=stage, use_graph=use_graph)
+    if use_graph:
+        try:
+            for length in lengths:
+                L.check(lib.mi_graph_launch(entries[length]["graph"], stream), "mi_graph_launch")
+        finally:
+            if noise_dev is not None:          # one-off graphs (injected noise buffer): the execs must outlive their replays
+                for entry in entries.values():
+                    destroy_graph(entry, ws.dev)
+    else:
+        for _ in range(m_steps):
+            entries[lengths[0]]["step"]()
+    if group:
+        # the sticky error word goes to pinned host memory behind the stage's last launch; Imagen._poll_status reads it once this call's event has fired
+        st.group_err_host.copy_(st.group_sync[8:12].view(torch.int32), non_blocking=True)
+        im._status_stages.append((st, stage, (B, H, W)))
+    if not finalize:
+        return None
+    img = torch.empty(shape, dtype=torch.float32, device=ws.dev)
+    L.check(lib.mi_finalize_images(L.ptr(ws.x), L.ptr(img), B * n, 1 if im.auto_normalize_img else 0, stream), "mi_finalize_images")
+    return img
+
+
+def _loop_entry(im, unet, st, ws, gkey, per, *, B, n, T, two, combine, cond_scale, rescale, sched, kind, group, k_lo, k_hi, w, noise_dev, seed,
+                sample0, stage, use_graph):
+    """The cached (or, for injected noise and eager runs, one-off) entry of ``per`` steps of p_sample_loop: dict(step, graph, per)."""
+    lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
+    entry = st.graphs.get(gkey) if (use_graph and noise_dev is None) else None
     if entry is None:
         # the radix select's first pass rides on the producer of x0; st.hist is zero on allocation and every mi_quantile_fwd leaves it zeroed again
         cp = L.MiCfgX0Params(B, n, L.ptr(ws.pred), 1 if combine else 0, float(cond_scale), L.ptr(ws.x), L.ptr(st.coef), L.ptr(st.t_state), 0, L.ptr(st.x0), L.ptr(st.hist))
@@ -260,23 +419,30 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
             st.group_sync = torch.zeros(lib.mi_sampler_group_sync_bytes(B, n), dtype=torch.uint8, device=ws.dev)   # this workspace's launches only
             st.group_err_host = torch.zeros(1, dtype=torch.int32).pin_memory() if L.backend() == "hip-gfx950" else torch.zeros(1, dtype=torch.int32)
         launch, advance = tail_launcher(st, ws, kind, cp, qp, pp, stream)
-        rp = None
-        if rescale:                              # phi and the scale are baked into the launches (gkey)
-            if st.rescale_partials is None:
-                st.rescale_partials = torch.zeros(B, lib.mi_cfg_rescale_chunks(n), 4, dtype=torch.float64, device=ws.dev)
+        rp, sps = None, {}
+        if rescale and st.rescale_partials is None:
+            st.rescale_partials = torch.zeros(B, lib.mi_cfg_rescale_chunks(n), 4, dtype=torch.float64, device=ws.dev)
+        if rescale and not sched:                # phi and the scale are baked into the launches (gkey)
             rp = C.byref(L.MiCfgRescaleParams(B, n, L.ptr(ws.pred), float(cond_scale), rescale, L.ptr(st.rescale_partials)))
+
+        def sched_params(k):                     # phi is baked in, the scales are read from st.scale_tab at step *t_state - k
+            if k not in sps:
+                sps[k] = L.MiCfgSchedParams(B, n, L.ptr(ws.pred), L.ptr(st.scale_tab), L.ptr(st.t_state), k, rescale, L.ptr(st.rescale_partials) if rescale else 0)
+            return C.byref(sps[k])
 
         def one_step(k=0, by=1):                 # step *t_state - k, then the device-resident step moves by `by`
             eng.run_step(ws, stream, t_off=k)
             if rp is not None:
                 L.check(lib.mi_cfg_rescale_stats_fwd(rp, stream), "mi_cfg_rescale_stats_fwd")
                 L.check(lib.mi_cfg_rescale_apply_fwd(rp, stream), "mi_cfg_rescale_apply_fwd")
+            elif sched and rescale:
+                L.check(lib.mi_cfg_sched_rescale_stats_fwd(sched_params(k), stream), "mi_cfg_sched_rescale_stats_fwd")
+                L.check(lib.mi_cfg_sched_rescale_apply_fwd(sched_params(k), stream), "mi_cfg_sched_rescale_apply_fwd")
+            elif sched:
+                L.check(lib.mi_cfg_sched_combine_fwd(sched_params(k), stream), "mi_cfg_sched_combine_fwd")
             launch(k)
             if by:
                 advance(by)
-        # `per` steps per captured graph (one replay boundary, ~9 us of idle GPU, per graph): step k addresses *t_state - k, one advance per graph
-        cap = int(os.environ.get("MINIMAGEN_STEPS_PER_GRAPH", "5"))
-        per = next(k for k in (5, 4, 3, 2, 1) if k <= cap and T % k == 0)
         entry = dict(step=one_step, graph=None, per=per)
         if use_graph:
             offsets = eng.step_offsets_supported(ws)
@@ -290,23 +456,5 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
             L.check(rc, "mi_graph_end")
             entry["graph"] = g
             if noise_dev is None:
-                while len(st.graphs) >= 8:                   # bounded: one exec per (guidance, threshold, shard offset) combination
-                    destroy_graph(st.graphs.pop(next(iter(st.graphs))), ws.dev)
                 st.graphs[gkey] = entry
-    if use_graph:
-        try:
-            for _ in range(T // entry["per"]):
-                L.check(lib.mi_graph_launch(entry["graph"], stream), "mi_graph_launch")
-        finally:
-            if noise_dev is not None:          # one-off graph (injected noise buffer): the exec must outlive its replays
-                destroy_graph(entry, ws.dev)
-    else:
-        for _ in range(T):
-            entry["step"]()
-    img = torch.empty(shape, dtype=torch.float32, device=ws.dev)
-    L.check(lib.mi_finalize_images(L.ptr(ws.x), L.ptr(img), B * n, 1 if im.auto_normalize_img else 0, stream), "mi_finalize_images")
-    if group:
-        # the sticky error word goes to pinned host memory behind the stage's last launch; Imagen._poll_status reads it once this call's event has fired
-        st.group_err_host.copy_(st.group_sync[8:12].view(torch.int32), non_blocking=True)
-        im._status_stages.append((st, stage, (B, H, W)))
-    return img
+    return entry
