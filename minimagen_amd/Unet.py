@@ -6,6 +6,7 @@ from dataclasses import dataclass
 from typing import List, Union
 
 import warnings
+import weakref
 
 import torch
 import torch.nn.functional as F
@@ -169,6 +170,10 @@ class Unet(nn.Module):
         train_ops.invalidate(self)
         return out
 
+    def __getstate__(self):
+        """copies and pickles carry no engine (its workspaces and raw graph handles have ONE owner): a copy builds its own on first use"""
+        return {**self.__dict__, '_engine': None}
+
     def _apply(self, fn, *args, **kwargs):
         before = [t.data_ptr() for t in self.parameters()]
         out = super()._apply(fn, *args, **kwargs)           # .to() / .cuda() / .float(): the packed copies point at the old storage ...
@@ -249,18 +254,19 @@ class Unet(nn.Module):
             t = t + torch.where(keep[:, None], text_hiddens, self.null_text_hidden.to(t.dtype))
             c = torch.cat((tokens, text_tokens), dim=-2)
         c = self.norm_cond(c)
+        slices = {}                 # ResnetBlock -> its slice of the stacked time MLP's output
         if dev_path:
             # the step is bound by its launch count: the ResnetBlocks' time MLPs (SiLU -> Linear(time_cond_dim, 2 dim_out), layers.py:386-391, one
             # per block, all of the same t) run as ONE linear layer over the stacked weights -- 4 launches instead of 2 per block, and one
             # matrix product per direction in the backward instead of two per block; each block reads its slice (ResnetBlock.forward)
-            rbs = self.__dict__.get("_mi_time_blocks")
-            if rbs is None:
-                rbs = self.__dict__["_mi_time_blocks"] = [m for m in self.modules() if isinstance(m, ResnetBlock) and m.time_mlp is not None]
+            st = train_ops.step_state(self)
+            if st.time_blocks is None:      # (weak references: the side table's values keep no module or parameter alive)
+                st.time_blocks = [weakref.ref(m) for m in self.modules() if isinstance(m, ResnetBlock) and m.time_mlp is not None]
+            rbs = [r() for r in st.time_blocks]
             if len(rbs) > 1:
                 lins = [m.time_mlp[1] for m in rbs]
                 allss = F.linear(F.silu(t), torch.cat([l.weight for l in lins], 0), torch.cat([l.bias for l in lins], 0))
-                for m, part in zip(rbs, allss.split([l.out_features for l in lins], dim=1)):
-                    m.__dict__["_mi_scale_shift"] = part
+                slices = dict(zip(rbs, allss.split([l.out_features for l in lins], dim=1)))
         # ---- trunk (Unet.py:396-472)
         lowres = lowres_cond_img if self.lowres_cond else None
         if dev_path and train_ops.crossembed_supported(self.init_conv, x, lowres):
@@ -271,29 +277,26 @@ class Unet(nn.Module):
         for pre, first, blocks, attn, post in self.downs:
             if exists(pre):
                 x = resample(pre, x)
-            x = first(x, t, c)
+            x = first(x, t, c, scale_shift_pre=slices.get(first))
             for blk in blocks:
-                x = blk(x, t)
+                x = blk(x, t, scale_shift_pre=slices.get(blk))
                 hiddens.append(x)
             x = attn(x)
             hiddens.append(x)
             if exists(post):
                 x = resample(post, x)
-        x = self.mid_block1(x, t, c)
+        x = self.mid_block1(x, t, c, scale_shift_pre=slices.get(self.mid_block1))
         if exists(self.mid_attn):
             x = self.mid_attn(x)
-        x = self.mid_block2(x, t, c)
+        x = self.mid_block2(x, t, c, scale_shift_pre=slices.get(self.mid_block2))
         with_skip = lambda v: torch.cat((v, hiddens.pop() * self.skip_connect_scale), dim=1)
         for first, blocks, attn, up in self.ups:
-            x = first(with_skip(x), t, c)
+            x = first(with_skip(x), t, c, scale_shift_pre=slices.get(first))
             for blk in blocks:
-                x = blk(with_skip(x), t)
+                x = blk(with_skip(x), t, scale_shift_pre=slices.get(blk))
             x = attn(x)
             x = conv3(up[1], up[0](x)) if isinstance(up, nn.Sequential) else up(x)
-        x = self.final_res_block(x, t)
-        if dev_path:
-            for m in self.__dict__.get("_mi_time_blocks", ()):          # (a block that did not run must not keep a slice of this step's graph)
-                m.__dict__.pop("_mi_scale_shift", None)
+        x = self.final_res_block(x, t, scale_shift_pre=slices.get(self.final_res_block))
         return conv3(self.final_conv, x)
 
     def forward_with_cond_scale(self, *args, cond_scale: float = 1., **kwargs) -> torch.Tensor:

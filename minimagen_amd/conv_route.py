@@ -1,6 +1,7 @@
-"""Which kernel, which tile, which flags: the launch policy of ``mi_conv_fwd`` in one place, for the engine's plans (``route``).  A leaf
-module: it knows the library's ``tile_cfg`` word (include/minimagen_hip.h) and nothing of the engine or the weights.  The tuning knobs stay
-``engine``'s module globals; it hands their current values in as a dict ``k`` keyed by ``KNOBS``.  (train_ops._conv3x3 still picks its tile itself.)"""
+"""Which kernel, which tile, which flags: the launch policy of ``mi_conv_fwd`` in one place, for the engine's plans (``route``) and for the
+training path's launches (``rp_code`` / ``direct_code``: the tile code only, no flags).  A leaf module: it knows the library's ``tile_cfg``
+word (include/minimagen_hip.h) and nothing of the engine or the weights.  The tuning knobs stay ``engine``'s module globals; it hands their
+current values in as a dict ``k`` keyed by ``KNOBS``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -87,6 +88,11 @@ def _rp_route(cin, cres, cout, H, W, stride, up2, wide_tiles):
     # four N tiles are only instantiated for the 8x32 tile.  Measured: 8x32 tiles for 8-channel layers at <= 64^2 (twice the workgroups) and for
     # images no wider than a tile; 16 output channels at 64^2 stay on 8x64 (B fragments staged per workgroup)
     return NARROW, (TILE_8X32 if cout > 16 or (H * W <= 64 * 64 and (W <= 32 or cout <= 8)) else TILE_8X64)
+
+
+def rp_code(cin: int, cout: int, H: int, W: int):
+    """-> (family, tile code) of a plain 3x3 stride-1 conv on the row-paired kernel, 8x32 tiles throughout the wide regime (the training path)"""
+    return _rp_route(cin, 0, cout, H, W, stride=1, up2=False, wide_tiles=False)
 
 
 def route(k: dict, *, batch: int, H: int, W: int, cin: int, cres: int, cout: int, ksize: int, stride: int, up2: bool, octets: bool, has_res: bool,

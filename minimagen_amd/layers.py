@@ -330,12 +330,12 @@ class ResnetBlock(_Container):
         self.res_conv = nn.Conv2d(dim, dim_out, 1) if dim != dim_out else Identity()
         self.groups = groups
 
-    def forward(self, x, time_emb=None, cond=None):
-        """layers.py:417-439"""
+    def forward(self, x, time_emb=None, cond=None, scale_shift_pre=None):
+        """layers.py:417-439; ``scale_shift_pre``: this block's ``time_mlp(time_emb)``, already computed (Unet._forward_train on the device runs
+        every block's time MLP as ONE stacked linear layer)"""
         scale_shift = None
-        pre = self.__dict__.pop("_mi_scale_shift", None)       # Unet._forward_train on the device: every block's time MLP as ONE stacked linear layer
         if exists(self.time_mlp) and exists(time_emb):
-            ss = pre if pre is not None else self.time_mlp(time_emb)
+            ss = scale_shift_pre if scale_shift_pre is not None else self.time_mlp(time_emb)
             scale_shift = ss[:, :, None, None].chunk(2, dim=1)
         h = self.block1(x)
         if exists(self.cross_attn):

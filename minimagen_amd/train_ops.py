@@ -15,7 +15,9 @@
   activation while it stages its operand tiles, so the activated tensor is never written to memory in either direction.
 
 Weights are re-packed into matrix-core fragments (``mi_pack_conv3``: one launch per weight and direction) when their version counter changes,
-i.e. once per optimiser step; the exponents of all layers come back with one host round trip (``begin_step``).  ``CrossEmbedLayer``: matrix-core forward + ``mi_crossembed_wgrad``.
+i.e. once per optimiser step; the exponents of all layers come back with one host round trip (``begin_step``).  The packs and everything else
+derived from the weights are kept in two weak side tables (``_WeightState`` per weight tensor, ``_StepState`` per module), never on the
+parameters or modules: copies and pickles of a module carry none of it.  ``CrossEmbedLayer``: matrix-core forward + ``mi_crossembed_wgrad``.
 ``CrossAttention`` (C < dim_head): the sampler's fold with the core on ``mi_folded_attn_fwd`` /
 ``mi_folded_attn_bwd`` (no score tensor, layers.CrossAttention._forward_folded).  The wide presets' attention layers (dim_head 64: the
 multi-query ``Attention`` and the unfolded ``CrossAttention``, C >= dim_head): the projections, null row and LayerNorms as before, the core on
@@ -28,12 +30,15 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import weakref
 
 import numpy as np
 import torch
 import torch.nn.functional as F
+from torch.utils.weak import WeakIdKeyDictionary
 
 from . import _lib as L
+from . import conv_route
 from . import packing as P
 
 ENABLED = os.environ.get("MINIMAGEN_TRAIN_HIP", "1") != "0"
@@ -84,11 +89,51 @@ def _pack_key(weight: torch.Tensor):
     return (weight._version, weight.data_ptr(), str(weight.device))
 
 
+class _WeightState:
+    """what the training path derived from the values of one conv weight tensor"""
+    __slots__ = ("key", "fwd", "bwd", "max_abs", "mark", "pattern")
+
+    def __init__(self):
+        self.key = self.fwd = self.bwd = None       # _pack_key the forward / adjoint packs were made at (None: no packs)
+        self.max_abs = None                         # max |w| as begin_step last brought it to the host: the fragment scaling (_weight_exp, _ce_tables)
+        self.mark = None                            # "values changed" compares this: the content fingerprint (synchronous mode) | the step number (lagged mode)
+        self.pattern = None                         # the fingerprint's fixed pseudo-random pattern
+
+    def renew(self, max_abs, mark):
+        """the values changed: a new scale and mark, and everything derived from the old values goes"""
+        self.max_abs, self.mark = max_abs, mark
+        self.key = self.fwd = self.bwd = None
+
+    def stale(self, w: torch.Tensor) -> bool:
+        return self.fwd is None or self.key != _pack_key(w)
+
+
+class _StepState:
+    """what ``begin_step`` keeps between the steps of one module (and ``crossembed_forward`` between those of one CrossEmbed layer)"""
+    __slots__ = ("counter", "sig", "dev", "k", "events", "host", "packs", "desc_key", "desc_dev", "ce_key", "ce_tables", "ce_index", "time_blocks")
+
+    def __init__(self, sig=None, dev=None):
+        self.counter = -1                                           # steps begun in the synchronous mode
+        self.sig, self.dev, self.k = sig, dev, 0                    # lagged mode: ids of the conv weights, their device, slot counter
+        self.events, self.host = [None, None], None                 # ... the two pinned buffers of maxima and the event behind each one's copy
+        self.packs, self.desc_key, self.desc_dev = {}, None, None   # ... id(w) -> pack buffers; the rows of the descriptor table and its device copy
+        self.ce_key, self.ce_tables, self.ce_index = None, None, {}     # CrossEmbed: what the Toeplitz tables were made from, the tables, the gather indices
+        self.time_blocks = None                                     # Unet._forward_train: weak references to the ResnetBlocks of the stacked time MLP
+
+
+# The side tables.  Keys are held weakly (tensors by identity), so an entry dies with its tensor / module; NO VALUE may hold a strong reference
+# to its key or to any parameter (ids and data pointers instead), or nothing would ever be collected.  Nothing derived is kept on the
+# parameters or modules themselves: copies and pickles of a module carry none of it.
+_WEIGHTS = WeakIdKeyDictionary()                    # conv weight tensor -> _WeightState
+_STEPS = weakref.WeakKeyDictionary()                # module -> _StepState
+weight_state, step_state = _WEIGHTS.get, _STEPS.get                 # for tests and tools: the record of a weight tensor / a module, or None
+
+
 def _packs(weight: torch.Tensor, exp=None):
-    """(forward pack, data-gradient pack) of a [Cout][Cin][3][3] parameter, cached on the parameter until it is updated in place"""
-    cached = getattr(weight, "_mi_train_packs", None)
-    if cached is not None and cached[0] == _pack_key(weight):
-        return cached[1], cached[2]
+    """(forward pack, data-gradient pack) of a [Cout][Cin][3][3] weight, kept in its _WeightState until it is updated in place"""
+    st = _WEIGHTS.setdefault(weight, _WeightState())
+    if not st.stale(weight):
+        return st.fwd, st.bwd
     w = weight.detach()
     if exp is None:
         exp = P.rp_weight_exponent(float(w.abs().max()))
@@ -96,7 +141,7 @@ def _packs(weight: torch.Tensor, exp=None):
     L.require_device(w)
     fwd = _Pack(w, exp, False)
     bwd = _Pack(w, exp, True)             # adjoint: W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx]
-    weight._mi_train_packs = (_pack_key(weight), fwd, bwd)
+    st.key, st.fwd, st.bwd = _pack_key(weight), fwd, bwd
     return fwd, bwd
 
 
@@ -116,40 +161,33 @@ def begin_step(module: torch.nn.Module):
     # The device -> host copy waits for the work queued before it (measured: 17.8 instead of 15.4 ms per SR step at B = 32, the host no longer
     # runs ahead of the GPU).  MINIMAGEN_TRAIN_FINGERPRINT=N checks every N-th step (0: never -- identity key only, round 3's behaviour);
     # weights whose identity key changed are always re-packed.
-    counter = module.__dict__["_mi_step_counter"] = module.__dict__.get("_mi_step_counter", -1) + 1
-    stale_id = any(getattr(w, "_mi_train_packs", None) is None or w._mi_train_packs[0] != _pack_key(w) for m, w in zip(convs, ws)
-                   if m.kernel_size == (3, 3) and m.stride == (1, 1))
-    check = FINGERPRINT_EVERY > 0 and counter % FINGERPRINT_EVERY == 0
+    step = _STEPS.setdefault(module, _StepState())
+    step.counter += 1
+    sts = [_WEIGHTS.setdefault(w, _WeightState()) for w in ws]
+    stale_id = any(st.stale(w) for m, w, st in zip(convs, ws, sts) if m.kernel_size == (3, 3) and m.stride == (1, 1))
+    check = FINGERPRINT_EVERY > 0 and step.counter % FINGERPRINT_EVERY == 0
     fp = None
     if check or stale_id:
         with torch.no_grad():
             det = [w.detach() for w in ws]
             # (max |w|, ||w||_2, ||w + r||_2) with r a fixed pseudo-random pattern per weight: the third term moves when values change sign or
             # place with both norms kept (w.data.neg_(), a channel permutation, an EMA copy of equal norm)
-            pats = []
-            for w in ws:                  # (cached on the parameter object itself)
-                r = getattr(w, "_mi_fp_pattern", None)
-                if r is None or r.shape != w.shape or r.device != w.device:
+            for w, st in zip(ws, sts):
+                if st.pattern is None or st.pattern.shape != w.shape or st.pattern.device != w.device:
                     g = torch.Generator().manual_seed(w.numel() * 2654435761 % (2 ** 31))
-                    r = (torch.rand(w.shape, generator=g) - 0.5).to(w.device)
-                    w._mi_fp_pattern = r
-                pats.append(r)
+                    st.pattern = (torch.rand(w.shape, generator=g) - 0.5).to(w.device)
+            pats = [st.pattern for st in sts]
             fp = torch.stack(torch._foreach_norm(det, float("inf")) + torch._foreach_norm(det, 2) + torch._foreach_norm(torch._foreach_add(det, pats), 2)).tolist()
     n = len(ws)
-    for k, (m, w) in enumerate(zip(convs, ws)):
+    for k, (m, w, st) in enumerate(zip(convs, ws, sts)):
         if fp is None:
             break
         mark = (fp[k], fp[n + k], fp[2 * n + k])
-        if getattr(w, "_mi_fingerprint", None) != mark:           # values changed behind the version counter: drop everything derived from them
-            w._mi_fingerprint = mark
-            for attr in ("_mi_train_packs", "_mi_ce_tables"):
-                if hasattr(w, attr):
-                    delattr(w, attr)
-        if m.kernel_size == (3, 3) and m.stride == (1, 1):
-            cached = getattr(w, "_mi_train_packs", None)
-            if cached is None or cached[0] != _pack_key(w):
-                with torch.no_grad():
-                    _packs(w, P.rp_weight_exponent(fp[k]))
+        if st.mark != mark:               # values changed behind the version counter
+            st.renew(fp[k], mark)
+        if m.kernel_size == (3, 3) and m.stride == (1, 1) and st.stale(w):
+            with torch.no_grad():
+                _packs(w, P.rp_weight_exponent(fp[k]))
 
 
 _DESC_DTYPE = np.dtype([("w", "u8"), ("frag", "u8"), ("generic", "u8"), ("Cout", "i4"), ("Cin", "i4"), ("adjoint", "i4"), ("exp", "i4"),
@@ -162,66 +200,62 @@ def _begin_step_lagged(module, convs, ws):
     previous step's max |w| leaves 2^8 of head room to the fp16 range (max |w'| in [128, 256) against 65504), far more than an optimiser step
     moves a weight.  Per step: one fused max launch + one asynchronous copy into pinned memory, read at the NEXT call -- by then the copy is a
     whole step old, so the host keeps running ahead of the GPU.  The first call (no history) waits for its own maxima, once."""
-    st = module.__dict__.get("_mi_lagged")
+    st = _STEPS.get(module)
     sig = tuple(id(w) for w in ws)
-    if st is None or st["sig"] != sig or st["dev"] != ws[0].device:
-        st = module.__dict__["_mi_lagged"] = dict(sig=sig, dev=ws[0].device, k=0, ev=[None, None],
-                                                  host=[torch.zeros(len(ws), dtype=torch.float32).pin_memory() for _ in range(2)])
-    slot = st["k"] & 1
+    if st is None or st.sig != sig or st.dev != ws[0].device:
+        st = _STEPS[module] = _StepState(sig, ws[0].device)
+        st.host = [torch.zeros(len(ws), dtype=torch.float32).pin_memory() for _ in range(2)]
+    slot = st.k & 1
     with torch.no_grad():
         mx = torch.stack(torch._foreach_norm([w.detach() for w in ws], float("inf")))
         known = None
-        if st["ev"][1 - slot] is not None:
-            st["ev"][1 - slot].synchronize()
-            known = st["host"][1 - slot].tolist()
-        st["host"][slot].copy_(mx, non_blocking=True)
-        ev = st["ev"][slot] = torch.cuda.Event()
+        if st.events[1 - slot] is not None:
+            st.events[1 - slot].synchronize()
+            known = st.host[1 - slot].tolist()
+        st.host[slot].copy_(mx, non_blocking=True)
+        ev = st.events[slot] = torch.cuda.Event()
         ev.record()
         if known is None or not all(math.isfinite(v) for v in known):
             ev.synchronize()
-            known = st["host"][slot].tolist()
-        st["k"] += 1
+            known = st.host[slot].tolist()
+        st.k += 1
         rows = []
-        packs = st.setdefault("packs", {})
         for m, w, mxk in zip(convs, ws, known):
-            w._mi_fingerprint = (mxk, st["k"])                 # _weight_exp / _ce_tables: the scale, and a mark that is new every step
-            for attr in ("_mi_train_packs", "_mi_ce_tables"):
-                if hasattr(w, attr):
-                    delattr(w, attr)
+            ws_ = _WEIGHTS.setdefault(w, _WeightState())
+            ws_.renew(mxk, st.k)                               # _weight_exp / _ce_tables: the scale, and a mark that is new every step
             if m.kernel_size == (3, 3) and m.stride == (1, 1):
                 exp = P.rp_weight_exponent(mxk)
                 if not w.is_contiguous():
                     _packs(w, exp)
                     continue
                 # the pack buffers live as long as the parameter keeps its storage: the descriptor table then only changes when an exponent does
-                pk = packs.get(id(w))
+                pk = st.packs.get(id(w))
                 if pk is None or pk[0] != (w.data_ptr(), tuple(w.shape)):
                     wd = w.detach()
-                    pk = packs[id(w)] = ((w.data_ptr(), tuple(w.shape)), _Pack(wd, exp, False, launch=False), _Pack(wd, exp, True, launch=False))
+                    pk = st.packs[id(w)] = ((w.data_ptr(), tuple(w.shape)), _Pack(wd, exp, False, launch=False), _Pack(wd, exp, True, launch=False))
                 pk[1].exp = pk[2].exp = exp
                 rows += [pk[1].desc(w, False), pk[2].desc(w, True)]
-                w._mi_train_packs = (_pack_key(w), pk[1], pk[2])
+                ws_.key, ws_.fwd, ws_.bwd = _pack_key(w), pk[1], pk[2]
         if rows:
             key = tuple(rows)
-            if st.get("desc_key") != key:                      # (first step, or an exponent moved: a small asynchronous upload through pinned memory)
+            if st.desc_key != key:                             # (first step, or an exponent moved: a small asynchronous upload through pinned memory)
                 arr = np.array(rows, dtype=_DESC_DTYPE)
                 host = torch.from_numpy(arr.view(np.uint8).reshape(-1)).pin_memory()
-                if st.get("desc_dev") is None or st["desc_dev"].numel() != host.numel():
-                    st["desc_dev"] = torch.empty(host.numel(), dtype=torch.uint8, device=ws[0].device)
-                st["desc_dev"].copy_(host, non_blocking=True)
-                st["desc_key"] = key
+                if st.desc_dev is None or st.desc_dev.numel() != host.numel():
+                    st.desc_dev = torch.empty(host.numel(), dtype=torch.uint8, device=ws[0].device)
+                st.desc_dev.copy_(host, non_blocking=True)
+                st.desc_key = key
             L.require_device(ws[0])
-            L.check(L.lib().mi_pack_conv3_multi(st["desc_dev"].data_ptr(), len(rows), 16, L.current_stream()), "mi_pack_conv3_multi")
+            L.check(L.lib().mi_pack_conv3_multi(st.desc_dev.data_ptr(), len(rows), 16, L.current_stream()), "mi_pack_conv3_multi")
 
 
 def invalidate(module: torch.nn.Module):
     """Drop every pack / table derived from the parameters under ``module`` (they are rebuilt on the next use).  ``begin_step`` notices
     changed values by itself; this is for callers that replace parameters outside a training step (``load_state_dict``, ``_apply``)."""
-    module.__dict__.pop("_mi_lagged", None)
+    for m in module.modules():
+        _STEPS.pop(m, None)
     for prm in module.parameters():
-        for attr in ("_mi_train_packs", "_mi_ce_tables", "_mi_fingerprint"):
-            if hasattr(prm, attr):
-                delattr(prm, attr)
+        _WEIGHTS.pop(prm, None)
 
 
 def _chan_stats(x: torch.Tensor) -> torch.Tensor:
@@ -230,6 +264,18 @@ def _chan_stats(x: torch.Tensor) -> torch.Tensor:
     st = torch.empty(B, Cc, 1, 2, dtype=torch.float64, device=x.device)
     L.check(L.lib().mi_chan_stats_fwd(x.data_ptr(), st.data_ptr(), B * Cc, H * W, L.current_stream()), "mi_chan_stats_fwd")
     return st
+
+
+def _tag_stats(t: torch.Tensor, stats: torch.Tensor):
+    """leave the channel statistics a kernel's epilogue wrote for ``t`` on the tensor itself: the only channel to its consumer that autograd
+    offers (the next Block's forward; the previous Block's backward, which receives this very tensor as its output gradient)"""
+    t._mi_stats = (stats, t._version)
+
+
+def _tagged_stats(t: torch.Tensor):
+    """the statistics left on ``t``: valid for this very tensor object while it has not been written since (else None: one statistics pass)"""
+    stats, version = getattr(t, "_mi_stats", (None, None))
+    return stats if (stats is not None and version == t._version and t.is_contiguous() and stats.shape[:2] == t.shape[:2]) else None
 
 
 _ZEROS = {}
@@ -271,10 +317,8 @@ def _conv3x3(x: torch.Tensor, pack: _Pack, bias, gn=None, ss=None, stats=None, w
         p.res0 = L.MiAct(res.data_ptr(), Cout, 0, 0, 1.0, 0, 0)
         keep.append(res)
     if rp:
-        wide = not (Cin <= 64 and Cout <= 32)
-        cfg = 6
-        if wide or Cout > 16 or (H * W <= 64 * 64 and (W <= 32 or Cout <= 8)):
-            cfg = 7
+        family, cfg = conv_route.rp_code(Cin, Cout, H, W)
+        wide = family == conv_route.WIDE
         p.w_rp, p.w_rp_exp = pack.frag.data_ptr(), pack.exp
         if wide:
             coef = torch.empty(B, Cin, 4, dtype=torch.float32, device=x.device)
@@ -285,7 +329,7 @@ def _conv3x3(x: torch.Tensor, pack: _Pack, bias, gn=None, ss=None, stats=None, w
         if wide:
             L.check(lib.mi_gn_coef_fwd(C.byref(p), L.current_stream()), "mi_gn_coef_fwd (training)")
     else:
-        p.tile_cfg = 0 if (W >= 64 and H * W > 64 * 64) else 2
+        p.tile_cfg = conv_route.direct_code(H, W)
     out_stats = None
     if want_stats:                  # the epilogue's per-tile partial statistics of the OUTPUT: the next Block reads them instead of a statistics pass
         th, tw = C.c_int(), C.c_int()
@@ -338,7 +382,7 @@ def _block_bwd(x, da, stats, gamma, beta, groups, eps, ss):
     dx_stats = torch.empty(B, Cc, nchunk, 2, dtype=torch.float64, device=x.device)
     p.uv, p.dx, p.dgamma, p.dbeta, p.dss, p.dx_stats = uv.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), L.ptr(dss), dx_stats.data_ptr()
     L.check(lib.mi_block_bwd(C.byref(p), L.current_stream()), "mi_block_bwd")
-    dx._mi_stats = (dx_stats, dx._version)        # the previous Block's backward receives this very tensor as its output gradient
+    _tag_stats(dx, dx_stats)
     return dx, dgamma, dbeta, dss
 
 
@@ -373,9 +417,7 @@ class _BlockFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         dx = dgamma = dbeta = dscale = dshift = dw = db = None
         if any(need[:5]):
-            tag = getattr(dy, "_mi_stats", None)          # left by the consumer Block's backward when dy is its dx, unmodified
-            dy_stats = tag[0] if (tag is not None and tag[1] == dy._version and tag[0].shape[:2] == dy.shape[:2]) else None
-            da = _conv3x3(dy, bwd, None, stats=dy_stats)
+            da = _conv3x3(dy, bwd, None, stats=_tagged_stats(dy))         # left by the consumer Block's backward when dy is its dx, unmodified
             dx, dgamma, dbeta, dss = _block_bwd(x, da, stats, gamma, beta, ctx.groups, ctx.eps, ss)
             if dss is not None:
                 Cc = x.shape[1]
@@ -414,22 +456,20 @@ class _ConvFn(torch.autograd.Function):
         return dx, (dw if need[1] else None), db, None
 
 
-def _ce_tables(convs, channels: int):
-    """Toeplitz fragment tables of the matrix-core CrossEmbed kernel (packing.pack_crossembed_mfma), one per input half, cached on the first
-    member's weight until any member is updated; ONE device->host copy of the (small) weights per optimiser step"""
-    key = tuple((_pack_key(c.weight), getattr(c.weight, "_mi_fingerprint", None)) for c in convs)
-    cached = getattr(convs[0].weight, "_mi_ce_tables", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
+def _ce_tables(layer, channels: int):
+    """Toeplitz fragment tables of the matrix-core CrossEmbed kernel (packing.pack_crossembed_mfma), one per input half, kept in the layer's
+    _StepState until any member conv is updated; ONE device->host copy of the (small) weights per optimiser step"""
+    convs, st = layer.convs, _STEPS.setdefault(layer, _StepState())
+    wst = [_WEIGHTS.get(c.weight) or _WeightState() for c in convs]
+    key = tuple((_pack_key(c.weight), s.max_abs, s.mark) for c, s in zip(convs, wst))
+    if st.ce_key == key:
+        return st.ce_tables
     dev = convs[0].weight.device
-    marks = [getattr(c.weight, "_mi_fingerprint", None) for c in convs]
-    if LAGGED and dev.type == "cuda" and all(m is not None and len(m) == 2 for m in marks):
+    if LAGGED and dev.type == "cuda" and all(isinstance(s.mark, int) for s in wst):
         # begin_step's lagged mode: tables gathered on the device from the current weights, scaled by the exponents of the previous step's
         # whole-tensor maxima (>= the packed channel slice's own: the head room only grows) -- no device -> host copy
-        idxs = getattr(convs[0].weight, "_mi_ce_index", None)
-        if idxs is None:
-            idxs = convs[0].weight._mi_ce_index = {}
-        exps = [P.rp_weight_exponent(m[0]) for m in marks]
+        idxs = st.ce_index
+        exps = [P.rp_weight_exponent(s.max_abs) for s in wst]
         tabs = {}
         with torch.no_grad():
             for chan0 in range(0, convs[0].in_channels, channels):
@@ -437,7 +477,7 @@ def _ce_tables(convs, channels: int):
                 if ik not in idxs:
                     idxs[ik] = P.crossembed_mfma_gather_index([c.weight.shape for c in convs], chan0, channels).to(dev)
                 tabs[chan0] = (P.pack_crossembed_mfma_device([c.weight for c in convs], idxs[ik], exps), exps)
-        convs[0].weight._mi_ce_tables = (key, tabs)
+        st.ce_key, st.ce_tables = key, tabs
         return tabs
     with torch.no_grad():
         flat = torch.cat([c.weight.detach().reshape(-1) for c in convs]).cpu()
@@ -450,7 +490,7 @@ def _ce_tables(convs, channels: int):
     for chan0 in range(0, convs[0].in_channels, channels):
         tab, exps = P.pack_crossembed_mfma(ws, chan0, channels)
         tabs[chan0] = (tab.to(dev, non_blocking=True), exps)
-    convs[0].weight._mi_ce_tables = (key, tabs)
+    st.ce_key, st.ce_tables = key, tabs
     return tabs
 
 
@@ -513,7 +553,7 @@ class _CrossEmbedFn(torch.autograd.Function):
 
 def crossembed_forward(layer, x: torch.Tensor, lowres) -> torch.Tensor:
     cv = layer.convs
-    tabs = _ce_tables(cv, x.shape[1])
+    tabs = _ce_tables(layer, x.shape[1])
     return _CrossEmbedFn.apply(x, lowres, tabs, cv[0].weight, cv[0].bias, cv[1].weight, cv[1].bias, cv[2].weight, cv[2].bias)
 
 
@@ -700,15 +740,12 @@ def block_forward(block, x: torch.Tensor, scale_shift=None, residual=None) -> to
         h = x if scale is None else x * (scale + 1) + shift
         out = _ConvFn.apply(F.silu(h), conv.weight, conv.bias)
         return out if residual is None else out + residual
-    # statistics handed over by the Block that produced x (block1 -> block2 of a ResnetBlock without cross-attention): valid for this very tensor
-    # object while it has not been written since
-    tag = getattr(x, "_mi_stats", None)
-    x_stats = tag[0] if (tag is not None and tag[1] == x._version and x.is_contiguous() and tag[0].shape[:2] == x.shape[:2]) else None
+    x_stats = _tagged_stats(x)      # handed over by the Block that produced x (block1 -> block2 of a ResnetBlock without cross-attention)
     fuse = residual_fusable(block, x, residual)
     out, out_stats = _BlockFn.apply(x, gnm.weight, gnm.bias, scale, shift, conv.weight, conv.bias, gnm.num_groups, gnm.eps, x_stats, residual if fuse else None)
     if residual is not None and not fuse:
         return out + residual
-    out._mi_stats = (out_stats, out._version)
+    _tag_stats(out, out_stats)
     return out
 
 
@@ -718,8 +755,8 @@ def conv3x3_forward(conv: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
 
 def _weight_exp(weight: torch.Tensor):
     """exponent of the fragment scaling from the max |w| that begin_step() already brought to the host (None: _packs fetches it)"""
-    mark = getattr(weight, "_mi_fingerprint", None)
-    return P.rp_weight_exponent(mark[0]) if mark is not None else None
+    st = _WEIGHTS.get(weight)
+    return P.rp_weight_exponent(st.max_abs) if st is not None and st.max_abs is not None else None
 
 
 def is_conv1x1(m, x=None) -> bool:

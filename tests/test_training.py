@@ -495,7 +495,7 @@ def test_training_packs_notice_updates_made_through_data():
     assert b is not a                                                  # ... but not to the fingerprint
     assert torch.equal(b.generic.reshape(8, 3, 3, -1)[..., :8], conv.weight.detach().permute(1, 2, 3, 0))
     train_ops.invalidate(conv)
-    assert not hasattr(conv.weight, "_mi_train_packs")
+    assert train_ops.weight_state(conv.weight) is None and train_ops.step_state(conv) is None
 
 
 def test_cross_attention_folded_training_form_equals_the_reference_form():
@@ -700,8 +700,8 @@ def test_lagged_scales_never_leave_a_stale_pack():
         y = train_ops.conv3x3_forward(conv, x)
         ref = F.conv2d(x.double(), conv.weight.detach().double(), conv.bias.detach().double(), padding=1)
         assert (y.double() - ref).abs().max() < 2e-6 * float(ref.abs().max()), factor
-    st = conv.__dict__["_mi_lagged"]
-    assert st["k"] == 4 and conv.weight._mi_fingerprint[1] == 4
+    st = train_ops.step_state(conv)
+    assert st.k == 4 and train_ops.weight_state(conv.weight).mark == 4
     # a whole training step, lagged against synchronous scales: same loss, same gradients (the scale is an exact power of two either way)
     torch.manual_seed(9)
     im = Imagen((Unet(**BASE), Unet(**SR)), text_encoder_name="t5_small", image_sizes=(32, 64), timesteps=60).train().to(dev)
