@@ -498,6 +498,16 @@ int mi_inpaint_prepare_fwd(const float* img, float* known, int B, int n, int nor
 /* N(0,1) fill with the same generator as mi_posterior_fwd (x_T, low-res augmentation noise) */
 int mi_randn_fill(float* out, int B, int n, uint64_t seed, int sample0, int stream_id, void* stream);
 
+/* the starting point of a loop that begins at an image of the caller's (Imagen.sample(init_images=), not in the reference): per element
+ *   y' = clamp(img, 0, 1), then *2-1 when normalize != 0 (NaN stays NaN, as mi_inpaint_prepare_fwd)
+ *   x  = fadd(fmul(a, y'), fmul(b, z))        every operation rounded on its own
+ * img_at_size, x: [B][n] (img already at the stage's size); z = noise[b][i], or with noise == NULL the draw mi_randn_fill(x, B, n, seed,
+ * sample0, stream_id) would have written to x[b][i] -- bit for bit, so the launch replaces that fill.  x may not alias img_at_size or noise.
+ * 16-byte accesses when n % 4 == 0 and every pointer is 16-byte aligned, element by element otherwise.  MI_ERR_INVALID for a NULL image or
+ * x, B <= 0 or n <= 0.  Added within ABI 12 (scalar arguments: no struct, no existing entry changed). */
+int mi_init_noise_fwd(const float* img_at_size, float* x, int B, int n, int normalize, float a, float b, uint64_t seed, int sample0, int stream_id,
+                      const float* noise, void* stream);
+
 /* img.clamp_(-1,1); then (img+1)*0.5 when unnormalize != 0   (Imagen.py:418-420) */
 int mi_finalize_images(const float* x, float* out, int64_t total, int unnormalize, void* stream);
 

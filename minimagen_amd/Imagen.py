@@ -291,6 +291,44 @@ class Imagen(nn.Module):
             inpaint = (inpaint_images, m.to(torch.uint8))
         return start, stop, inpaint, start_image
 
+    def _parse_init(self, batch_size: int, init_images, init_strength, solvers, first_stage: int, end_stage: int):
+        """-> (init images float32 [B, C, H, W] still where the caller has them, or None; per stage None -- the stage starts from pure noise -- or
+        a0, the number of loop steps it skips: sampler.init_start_step).  A strength for a stage the call does not run is ignored.  Host only;
+        raises ValueError on bad or inconsistent values."""
+        n_stages = len(self.unets)
+        if init_images is None and init_strength is None:
+            return None, [None] * n_stages
+        if init_images is None or init_strength is None:
+            raise ValueError("init_images and init_strength go together")
+        t = init_images
+        if not torch.is_tensor(t) or t.dim() != 4 or not t.is_floating_point():
+            raise ValueError(f"init_images must be a float tensor [B, {self.channels}, H, W]")
+        if t.shape[0] != batch_size:
+            raise ValueError(f"init_images: batch {t.shape[0]} does not match the text batch {batch_size}")
+        if t.shape[1] != self.channels:
+            raise ValueError(f"init_images: {t.shape[1]} channels, the model has {self.channels}")
+        if t.shape[2] != t.shape[3] or t.shape[2] < 1:
+            raise ValueError(f"init_images must be square, got {tuple(t.shape[2:])}")
+        if isinstance(init_strength, (list, tuple)):
+            strengths = list(init_strength)
+            if len(strengths) != n_stages:
+                raise ValueError(f"init_strength needs one entry per stage ({n_stages}), got {len(strengths)}")
+        else:
+            if init_strength is None or isinstance(init_strength, bool) or not isinstance(init_strength, (int, float)):
+                raise ValueError(f"init_strength must be a number in (0, 1] or a list with a number or None per stage, got {init_strength!r}")
+            strengths = [init_strength] * n_stages
+        starts = [None] * n_stages
+        for stage, v in enumerate(strengths):
+            if v is None:
+                continue
+            n_steps = self.noise_schedulers[stage].num_timesteps if solvers[stage] is None else solvers[stage][0]
+            a0 = S.init_start_step(n_steps, v)                   # (validates the value of every entry, run or not)
+            if first_stage <= stage < end_stage:
+                starts[stage] = a0
+        if all(a0 is None for a0 in starts):
+            raise ValueError("init_strength: every stage the call runs has None")
+        return t.detach().to(torch.float32), starts
+
     def _parse_guidance(self, batch_size: int, cond_scale, texts, text_embeds, text_masks, negative_texts, negative_text_embeds,
                         negative_text_masks, guidance_rescale, guided: bool = None):
         """``guided``: whether any step of the call is guided (None: ``cond_scale`` != 1, a call without a guidance schedule).
@@ -419,7 +457,8 @@ class Imagen(nn.Module):
                inpaint_images: torch.Tensor = None, inpaint_masks: torch.Tensor = None, start_image: torch.Tensor = None,
                start_at_stage: int = None, stop_at_stage: int = None,
                negative_texts: Union[str, List[str]] = None, negative_text_embeds: torch.Tensor = None, negative_text_masks: torch.Tensor = None,
-               guidance_rescale: float = None, guidance_interval=None, guidance_schedule=None):
+               guidance_rescale: float = None, guidance_interval=None, guidance_schedule=None,
+               init_images: torch.Tensor = None, init_strength=None):
         """minimagen/Imagen.py:424-510.  Private keyword-only extras (not in the reference): ``_noise(shape)`` injects a
         host noise stream in the reference's draw order (parity runs); otherwise noise is Philox keyed by
         (``_seed``, ``_sample_offset`` + row, stage, step, element) so a sharded batch reproduces the unsharded one;
@@ -468,20 +507,36 @@ class Imagen(nn.Module):
         A step whose scales are all exactly 1 is unguided (negative prompts and ``guidance_rescale``, the identity there, are skipped; they
         need one guided step somewhere).  A stage moves between its B-row and its 2 B-row workspace at the run boundaries (x, the
         dpmpp_2m history and the step index are handed over; same noise stream); an interval of (0, 1), a constant schedule s or an
-        all-ones schedule IS the call with ``cond_scale`` = s / 1.  Bad values, lengths and shapes raise ValueError before anything is launched."""
+        all-ones schedule IS the call with ``cond_scale`` = s / 1.  Bad values, lengths and shapes raise ValueError before anything is launched.
+
+        Starting from an image (SDEdit / "img2img"; keyword-only, not in the reference).  ``init_images`` ([B, C, H, W]
+        float in [0, 1], square, any size; resized per stage like ``inpaint_images``) with ``init_strength`` = s in (0, 1] for every stage, or
+        a list with s or None (that stage starts from pure noise, as without the keywords) per stage: a stage of S loop steps skips its
+        first a0 = S - m, m = min(S, max(1, floor(s S + 0.5))) (sampler.init_start_step), and runs the other m from
+        x = sqrt(abar_tau) y' + sqrt(1 - abar_tau) eps at tau = the trained timestep of step a0 (GaussianDiffusion.init_start_coefs) -- eps IS
+        the stage's own x_T draw and every other draw keeps its index in the full loop, so a sharded batch reproduces the unsharded one and
+        ``_noise`` is called in the order it is called today.  With every ``sampler`` / ``sample_steps`` ('dpmpp_2m': the first executed
+        step is first order), with inpainting (blend 0 at the starting level), with ``start_image`` / ``start_at_stage`` / ``stop_at_stage`` (a
+        strength for a stage that does not run is ignored) and with the guidance keywords, whose intervals and schedules stay indexed by the
+        step of the FULL loop ([S] / [S, B] keep their shape, entry a0 is the first one executed; "one guided step somewhere" means an
+        executed one).  One strength per stage, not per row; no RePaint resampling.  Bad values raise ValueError before anything is
+        launched; a call without the two goes through exactly the workspaces, states, tables, graph keys and launches it goes through today.
+        Nothing here has been tried on a trained model: what is checked is the arithmetic."""
         solvers = self._parse_solver(sample_steps, sampler, sampler_eta)
         rescale, negative, scale_tabs = 0., None, None
         if exists(text_embeds) or exists(texts):
             n_rows = text_embeds.shape[0] if exists(text_embeds) else len(texts)
             first_stage, end_stage, inpaint, start_image = self._parse_inpaint(n_rows, inpaint_images, inpaint_masks, start_image, start_at_stage, stop_at_stage)
+            init_images, init_starts = self._parse_init(n_rows, init_images, init_strength, solvers, first_stage, end_stage)
             scale_tabs = self._parse_guidance_schedule(n_rows, cond_scale, solvers, guidance_interval, guidance_schedule)
             guided = None
-            if scale_tabs is not None:
-                guided = any(cond_scale != 1. if scale_tabs[s] is None else bool((scale_tabs[s] != 1.).any()) for s in range(first_stage, end_stage))
+            if scale_tabs is not None:                           # (of the steps a stage executes: a loop that starts at an init image skips its first ones)
+                guided = any(cond_scale != 1. if scale_tabs[s] is None else bool((scale_tabs[s][init_starts[s] or 0:] != 1.).any())
+                             for s in range(first_stage, end_stage))
             rescale, negative = self._parse_guidance(n_rows, cond_scale, texts, text_embeds, text_masks,
                                                      negative_texts, negative_text_embeds, negative_text_masks, guidance_rescale, guided)
         call_args = dict(guidance_interval=guidance_interval, guidance_schedule=guidance_schedule, negative_texts=negative_texts, negative_text_embeds=negative_text_embeds, negative_text_masks=negative_text_masks,
-                         guidance_rescale=guidance_rescale, inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, start_image=start_image, start_at_stage=start_at_stage,
+                         guidance_rescale=guidance_rescale, init_images=init_images, init_strength=init_strength, inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, start_image=start_image, start_at_stage=start_at_stage,
                          stop_at_stage=stop_at_stage, sample_steps=sample_steps, sampler=sampler, sampler_eta=sampler_eta, texts=texts, text_masks=text_masks, text_embeds=text_embeds, cond_scale=cond_scale, lowres_sample_noise_level=lowres_sample_noise_level,
                          return_pil_images=return_pil_images, device=device, _noise=_noise, _seed=_seed, _sample_offset=_sample_offset,
                          _use_graph=_use_graph, _precision=_precision, _async=_async)
@@ -503,7 +558,9 @@ class Imagen(nn.Module):
         for stage in range(first_stage, end_stage):
             w_stage = None if scale_tabs is None else scale_tabs[stage]
             n_steps = self.noise_schedulers[stage].num_timesteps if solvers[stage] is None else solvers[stage][0]
-            plans[stage] = [('plain' if cond_scale == 1. else 'scalar', 0, n_steps, cond_scale)] if w_stage is None else S.guidance_plan(w_stage)
+            a0 = init_starts[stage] or 0                         # a stage that starts from an init image: the plan of the steps [a0, S) it executes
+            plans[stage] = [('plain' if cond_scale == 1. else 'scalar', a0, n_steps, cond_scale)] if w_stage is None else \
+                [(kind, a + a0, b + a0, scale) for kind, a, b, scale in S.guidance_plan(w_stage[a0:])]
         any_guided = any(kind != 'plain' for runs in plans.values() for kind, *_ in runs)
         assert not (any_guided and not self.can_classifier_guidance), \
             'imagen was not trained with conditional dropout, and thus one cannot use classifier free guidance (cond_scale anything other than 1)'
@@ -518,7 +575,9 @@ class Imagen(nn.Module):
             inpaint = tuple(t.to(device).contiguous() for t in inpaint) + (self.auto_normalize_img,)
         if start_image is not None:
             start_image = start_image.to(device).contiguous()
-        pixel_inputs = [t for t in (inpaint or ())[:2] + (start_image,) if t is not None]
+        if init_images is not None:
+            init_images = init_images.to(device).contiguous()
+        pixel_inputs = [t for t in (inpaint or ())[:2] + (start_image, init_images) if t is not None]
         if negative is not None:            # read by the stage streams like the captions (record_stream below)
             negative = tuple(None if t is None else t.to(device) for t in negative)
             pixel_inputs += [t for t in negative if t is not None]
@@ -574,8 +633,10 @@ class Imagen(nn.Module):
         stages = list(enumerate(zip(self.unets, self.sample_channels, self.image_sizes, self.noise_schedulers)))[first_stage:end_stage]
         known = {} if inpaint is None else dict(inpaint=inpaint)        # (a call without known pixels passes nothing new down)
         # ... and neither does a noise-predicting stage: only another objective names itself (it selects the stage's coefficient table)
-        extras = {stage: dict(known, **({} if self.pred_objectives[stage] == 'noise' else dict(objective=self.pred_objectives[stage])))
+        extras = {stage: dict(known, **({} if self.pred_objectives[stage] == 'noise' else dict(objective=self.pred_objectives[stage])),
+                              **({} if init_starts[stage] is None else dict(init=(init_images, self.auto_normalize_img))))
                   for stage, _ in stages}
+        starts = {stage: {} if init_starts[stage] is None else dict(start=init_starts[stage]) for stage, _ in stages}
         # guidance rescale reads both halves of the prediction: a workspace of its own that never folds the guidance into the U-Net's tail --
         # and so does a run whose scales come from a table; an unguided run (B rows) takes neither, nor the negative captions
         unfolded = {kind: dict(fold=False) if (kind == 'table' or (rescale and kind == 'scalar')) else {} for kind in keeps}
@@ -604,7 +665,7 @@ class Imagen(nn.Module):
                         ws.lowres_times.fill_(int(self.lowres_noise_schedule.num_timesteps * lowres_sample_noise_level))
                 if _noise is None:
                     begun[stage] = self._stage_begin(unet, (batch_size, self.channels, image_size, image_size), noise_scheduler=noise_scheduler,
-                                                     ws=wss[stage][plans[stage][0][0]], seed=_seed, sample0=_sample_offset, stage=stage, solver=solvers[stage], **extras[stage])
+                                                     ws=wss[stage][plans[stage][0][0]], seed=_seed, sample0=_sample_offset, stage=stage, solver=solvers[stage], **extras[stage], **starts[stage])
         # ---- pass 2: the cascade
         img, prev_done = start_image, None
         for stage, (unet, channel, image_size, noise_scheduler) in stages:
@@ -625,7 +686,8 @@ class Imagen(nn.Module):
                 loop = dict(noise_scheduler=noise_scheduler, noise_fn=_noise, seed=_seed, sample0=_sample_offset, stage=stage, use_graph=_use_graph,
                             solver=solvers[stage], **extras[stage])
                 if len(runs) == 1 and runs[0][0] != 'table':
-                    img = self._p_sample_loop(unet, shape, ws=ws, cond_scale=runs[0][3], begun=begun.get(stage), **loop, **rescaled[runs[0][0]])
+                    part = {} if init_starts[stage] is None else dict(steps=runs[0][1:3])          # (a run (a0, S) of the loop, like a plan's)
+                    img = self._p_sample_loop(unet, shape, ws=ws, cond_scale=runs[0][3], begun=begun.get(stage), **loop, **rescaled[runs[0][0]], **part)
                 else:
                     img = self._run_plan(unet, shape, runs, wss[stage], scale_tabs[stage], begun.get(stage), loop, rescaled)
                 if on_gpu:
@@ -668,8 +730,11 @@ class Imagen(nn.Module):
         run's workspace, issued here for injected noise -- one x_T and one draw per step, whatever workspaces the stage visits) -> the image."""
         first = workspaces[runs[0][0]]
         begin = {k: loop[k] for k in ('noise_scheduler', 'stage', 'solver', 'inpaint', 'objective') if k in loop}
+        if 'init' in loop:                                       # the first run starts at step a0 (and selects the state of a 'dpmpp_2m' loop by it)
+            begin['start'] = runs[0][1]
         if begun is None:
-            begun = self._stage_begin(unet, shape, ws=first, noise_fn=loop['noise_fn'], seed=loop['seed'], sample0=loop['sample0'], **begin)
+            begun = self._stage_begin(unet, shape, ws=first, noise_fn=loop['noise_fn'], seed=loop['seed'], sample0=loop['sample0'], **begin,
+                                      **({'init': loop['init']} if 'init' in loop else {}))
         st0, noise_dev = begun
         states = {runs[0][0]: st0}
         for kind, ws in workspaces.items():

@@ -322,6 +322,8 @@ def _bind(lib):
     lib.mi_inpaint_blend0_fwd.argtypes = [vp, i32, i32, vp, f32, f32, u64, i32, vp]
     lib.mi_inpaint_prepare_fwd.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, vp, i32, vp]
     lib.mi_randn_fill.argtypes = [vp, i32, i32, u64, i32, i32, vp]
+    lib.mi_init_noise_fwd.argtypes = [vp, vp, i32, i32, i32, f32, f32, u64, i32, i32, vp, vp]
+    lib.mi_init_noise_fwd.restype = i32
     lib.mi_finalize_images.argtypes = [vp, vp, i64, i32, vp]
     lib.mi_lowres_augment.argtypes = [vp, vp, vp, i64, f32, f32, i32, vp]
     lib.mi_gemm_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]

@@ -510,6 +510,27 @@ __global__ __launch_bounds__(256) void known_image_kernel(const float* img, floa
         out[i] = v;
     }
 }
+// the starting point of a loop that begins at an image of the caller's: x = a * y' + b * z with y' the image in the sampler's range (as
+// known_image_kernel) and z the draw randn_fill_kernel would have written there (same seed, row, stream, quad) or the injected one.
+// fadd(fmul, fmul), every operation rounded on its own; `vec`: n % 4 == 0 and 16-byte aligned pointers
+__global__ __launch_bounds__(256) void init_noise_kernel(const float* img, float* x, int n, int normalize, float a, float bcoef, unsigned long long seed,
+                                                         int sample0, int stream_id, const float* noise, int vec) {
+    const int b = blockIdx.y, nq = (n + 3) / 4;
+    const size_t ob = (size_t)b * n;
+    for (int qd = blockIdx.x * 256 + threadIdx.x; qd < nq; qd += gridDim.x * 256) {
+        float y[4], z[4];
+        ld_quad(img + ob, 4 * qd, n, vec != 0, y);
+        if (noise) ld_quad(noise + ob, 4 * qd, n, vec != 0, z);
+        else randn4(seed, (unsigned)(sample0 + b), (unsigned)stream_id, (unsigned)qd, z);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float v = y[e] != y[e] ? y[e] : fminf(fmaxf(y[e], 0.0f), 1.0f);
+            if (normalize) v = __fsub_rn(__fmul_rn(v, 2.0f), 1.0f);                  // helpers.py:105-110
+            y[e] = __fadd_rn(__fmul_rn(a, v), __fmul_rn(bcoef, z[e]));               // diffusion_model.py:142-147 (q_sample)
+        }
+        st_quad(x + ob, 4 * qd, n, vec != 0, y);                                     // (past the row's end: computed on zeros, not stored)
+    }
+}
 // the mask at a stage's size: nearest neighbour, source index floor(i * Hin / size) (F.interpolate(mode='nearest')); nonzero -> 1
 __global__ __launch_bounds__(256) void known_mask_kernel(const unsigned char* in, unsigned char* out, int Hin, int Win, int size) {
     const int b = blockIdx.y;
@@ -899,6 +920,16 @@ extern "C" int mi_step_set_mapped(int* t_state, int64_t* times, int B, int value
 extern "C" int mi_randn_fill(float* out, int B, int n, uint64_t seed, int sample0, int stream_id, void* stream) {
     hipLaunchKernelGGL(randn_fill_kernel, dim3(grid_for((n + 3) / 4, 256), B), dim3(256), 0, (hipStream_t)stream, out, n, (unsigned long long)seed, sample0, stream_id);
     return mi_check_launch("randn_fill_kernel");
+}
+
+extern "C" int mi_init_noise_fwd(const float* img_at_size, float* x, int B, int n, int normalize, float a, float b, uint64_t seed, int sample0, int stream_id,
+                                 const float* noise, void* stream) {
+    if (!img_at_size || !x || B <= 0 || n <= 0) { mi_set_error("mi_init_noise_fwd: empty"); return MI_ERR_INVALID; }
+    const uintptr_t bits = (uintptr_t)img_at_size | (uintptr_t)x | (uintptr_t)noise;
+    const int vec = ((n & 3) == 0 && (bits & 15) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(init_noise_kernel, dim3(grid_for((n + 3) / 4, 256), B), dim3(256), 0, (hipStream_t)stream, img_at_size, x, n, normalize, a, b,
+                       (unsigned long long)seed, sample0, stream_id, noise, vec);
+    return mi_check_launch("init_noise_kernel");
 }
 
 extern "C" int mi_finalize_images(const float* x, float* out, int64_t total, int unnormalize, void* stream) {

@@ -71,6 +71,19 @@ class GaussianDiffusion(nn.Module):
         a = self._abar64()[-1]
         return float(torch.sqrt(a).to(torch.float32)), float(torch.sqrt(1. - a).to(torch.float32))
 
+    def init_start_coefs(self, steps: int = None, start: int = 0):
+        """(a, b) = (sqrt(abar_tau), sqrt(1 - abar_tau)) as fp32 values at tau = tau_{S-1-start}, the trained timestep of the first step a loop
+        of S = ``steps`` steps (None: T, the default loop) executes when it skips its first ``start`` steps: the level an init image is noised
+        to (Imagen.sample(init_images=)).  fp64 from the betas, rounded once; ``start`` = 0 is known_start_coefs() -- and ``start`` >= 1 is
+        columns 6 and 7 of row S - start of the ``known`` table, the level behind step S - start."""
+        T = self.num_timesteps
+        S = T if steps is None else int(steps)
+        tau = torch.arange(T) if steps is None else self.sampling_timestep_map(S)
+        if isinstance(start, bool) or not isinstance(start, int) or not 0 <= start < S:
+            raise ValueError(f'start must be an int in [0, {S - 1}] for a loop of {S} steps, got {start!r}')
+        a = self._abar64()[int(tau[S - 1 - start])]
+        return float(torch.sqrt(a).to(torch.float32)), float(torch.sqrt(1. - a).to(torch.float32))
+
     OBJECTIVES = ('noise', 'x_start', 'v')
 
     @classmethod
@@ -123,7 +136,7 @@ class GaussianDiffusion(nn.Module):
             raise ValueError(f'sample_steps must be in [2, {T}] for a schedule of {T} timesteps, got {steps}')
         return torch.tensor([(2 * k * (T - 1) + (S - 1)) // (2 * (S - 1)) for k in range(S)], dtype=torch.int64)
 
-    def _sampler_tables64(self, steps: int, sampler: str = 'ddpm', eta: float = None, known: bool = False, objective: str = 'noise'):
+    def _sampler_tables64(self, steps: int, sampler: str = 'ddpm', eta: float = None, known: bool = False, objective: str = 'noise', start: int = 0):
         """sampler_tables before the rounding to fp32: (tau int64[S], abar float64[S], coef float64[S][8])"""
         self._check_objective(objective)
         if sampler not in self.SAMPLERS:
@@ -135,6 +148,8 @@ class GaussianDiffusion(nn.Module):
             raise ValueError(f'sampler_eta must be in [0, 1], got {eta}')
         tau = self.sampling_timestep_map(steps)
         T, S = self.num_timesteps, tau.numel()
+        if isinstance(start, bool) or not isinstance(start, int) or not 0 <= start < S:
+            raise ValueError(f'start must be an int in [0, {S - 1}] for a loop of {S} steps, got {start!r}')
         scale = 1000 / T
         betas = torch.linspace(scale * 0.0001, scale * 0.02, T, dtype=torch.float64)        # as __init__, kept in fp64
         a = torch.cumprod(1. - betas, dim=0)[tau]
@@ -158,7 +173,7 @@ class GaussianDiffusion(nn.Module):
                 h = lam[k - 1] - lam[k]
                 m = al[k - 1] * (1. - torch.exp(-h))
                 tab[k, 3] = sg[k - 1] / sg[k]
-                if k == S - 1:                               # first step: no history yet (DPM-Solver++ 1 = DDIM)
+                if k == S - 1 or k == S - 1 - start:         # first step (executed: a loop that skips ``start`` steps): no history yet (DPM-Solver++ 1 = DDIM)
                     tab[k, 2] = m
                 else:
                     r = (lam[k] - lam[k + 1]) / h
@@ -171,15 +186,18 @@ class GaussianDiffusion(nn.Module):
             tab[:, 0:2] = cols
         return tau, a, tab
 
-    def sampler_tables(self, steps: int, sampler: str = 'ddpm', eta: float = None, known: bool = False, objective: str = 'noise'):
+    def sampler_tables(self, steps: int, sampler: str = 'ddpm', eta: float = None, known: bool = False, objective: str = 'noise', start: int = 0):
         """(tau int64[S], coef float32[S][8]) for ``steps`` sampling steps over the trained timesteps tau: row k of ``coef`` is the step at
         timestep tau_k (the sampler walks k = S-1 .. 0).  With cN = column N (the naming of DESIGN.md section 14 and the C header): x0 = c0 x - c1 eps, then
         x' = c2 x0 + c3 x + c5 x0_prev + c4 z with the thresholded x0 of this and of the previous step.  'ddpm' is 'ddim' with eta = 1 (the reference's ancestral step when
         S = T); 'dpmpp_2m' is deterministic.  Everything in fp64 from the betas, rounded to fp32 once.  ``known``: plus c6 = sqrt(abar_{tau_{k-1}}) and
         c7 = sqrt(1 - abar_{tau_{k-1}}), the level an inpainting call re-imposes its known pixels at behind step k (row 0: exactly 1 and 0);
         without it columns 6 and 7 are zero and the table is what it was before the flag existed.  ``objective`` = 'v' / 'x_start': c0 and c1 turn
-        that prediction into x0 (sampler_coef_table); the solvers work on x0 and x only, so columns 2 .. 7 do not depend on it."""
-        tau, _, tab = self._sampler_tables64(steps, sampler, eta, known, objective)
+        that prediction into x0 (sampler_coef_table); the solvers work on x0 and x only, so columns 2 .. 7 do not depend on it.
+        ``start`` = a0 > 0: the loop skips its first a0 steps (an init image), so row S-1-a0 is the first one executed --
+        for 'dpmpp_2m' that row gets the first-order coefficients (no history yet: c2 = m, c5 = 0); every other row, every other sampler and
+        ``start`` = 0 are bit-identical to the table without the argument."""
+        tau, _, tab = self._sampler_tables64(steps, sampler, eta, known, objective, start)
         return tau, tab.to(torch.float32)
 
     def loss_weight_table(self, objective: str, min_snr_gamma: float = None) -> torch.Tensor:

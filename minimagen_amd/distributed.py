@@ -58,7 +58,9 @@ def sample_distributed(imagen, *, text_embeds: torch.Tensor, text_masks: Optiona
     like the step noise); ``start_at_stage`` / ``stop_at_stage`` go through (the gathered images then have the last stage's size that ran).
     ``negative_text_embeds`` / ``negative_text_masks`` (full batch) are sharded by the same bounds; ``guidance_rescale`` goes through (its
     statistics are per image, so sharding changes no bit).  ``guidance_interval`` goes through; of a ``guidance_schedule`` (one entry per
-    stage) every [S, B] entry (per row, full batch) is sharded along dimension 1 by the same bounds, everything else goes through."""
+    stage) every [S, B] entry (per row, full batch) is sharded along dimension 1 by the same bounds, everything else goes through.
+    ``init_images`` (full batch) is sharded with the captions' rows and ``init_strength`` goes through: the init noise is the stage's own
+    x_T draw, keyed by the global row like every other, so the gathered batch equals the unsharded call here too."""
     ws = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     batch = text_embeds.shape[0]
@@ -71,7 +73,7 @@ def sample_distributed(imagen, *, text_embeds: torch.Tensor, text_masks: Optiona
         size = imagen.image_sizes[(sample_kwargs.get("stop_at_stage") or len(imagen.image_sizes)) - 1]
         local = torch.zeros(0, imagen.channels, size, size, dtype=torch.float32, device=dev)
         return gather_samples(local, batch, group) if (gather and not _alone(ws)) else local
-    for name in ("inpaint_images", "inpaint_masks", "start_image", "negative_text_embeds", "negative_text_masks"):
+    for name in ("inpaint_images", "inpaint_masks", "start_image", "init_images", "negative_text_embeds", "negative_text_masks"):
         if sample_kwargs.get(name) is not None:
             sample_kwargs[name] = sample_kwargs[name][lo:hi].contiguous()
     schedule = sample_kwargs.get("guidance_schedule")

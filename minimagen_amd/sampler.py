@@ -47,6 +47,17 @@ def cubic_resize(ws, img, image_size: int, stream):
     return up
 
 
+def init_start_step(steps: int, strength: float) -> int:
+    """a0, the number of steps a loop of S = ``steps`` steps skips when it starts from an init image at ``strength`` in (0, 1]: it executes its
+    last m = min(S, max(1, floor(strength S + 0.5))) steps, a0 = S - m (strength 1: the whole loop).  Host only; raises ValueError."""
+    S = int(steps)
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0. < float(strength) <= 1.:
+        raise ValueError(f"init_strength must be a number in (0, 1], got {strength!r}")
+    if S < 1:
+        raise ValueError(f"steps must be positive, got {steps!r}")
+    return S - min(S, max(1, int(float(strength) * S + 0.5)))
+
+
 def guidance_scale_table(tau, T: int, B: int, cond_scale: float = 1., interval=None, schedule=None) -> torch.Tensor:
     """A stage's guidance scales in EXECUTION order (entry 0: the first step executed, the noisiest one), float64 [S] or [S, B] (per row; the
     caller's values as they are: a run at ONE scale is the call at that cond_scale, a table run rounds them to fp32).
@@ -123,7 +134,7 @@ class StageState:
     __slots__ = ("coef", "tau", "t_map", "x0_prev", "ext", "t_state", "x0", "hist", "s_q", "v_q", "seed_dev", "graphs",
                  "group_sync", "group_err_host", "group_failed", "group_heal", "known", "mask", "ip", "known_noise", "rescale_partials", "scale_tab", "scale_tab_host")
 
-    def __init__(self, sched, B: int, n: int, dev, solver=None, hw: int = None, objective: str = 'noise'):
+    def __init__(self, sched, B: int, n: int, dev, solver=None, hw: int = None, objective: str = 'noise', start: int = 0):
         self.tau = self.t_map = self.x0_prev = None     # the reference's loop has no step -> timestep map and no history
         self.known = self.mask = self.ip = self.known_noise = self.rescale_partials = self.scale_tab = self.scale_tab_host = None
         known = {} if hw is None else dict(known=True)
@@ -135,6 +146,8 @@ class StageState:
         if solver is None:
             self.coef = sched.sampler_coef_table(**known).to(dev).contiguous()
         else:
+            if start and solver[1] == 'dpmpp_2m':             # a loop that skips its first steps: the first one executed is first order
+                known['start'] = start
             self.tau, coef = sched.sampler_tables(solver[0], solver[1], solver[2] if solver[1] == 'ddim' else None, **known)
             self.coef = coef.to(dev).contiguous()
             self.t_map = self.tau.to(torch.int32).to(dev).contiguous()
@@ -159,12 +172,18 @@ class StageState:
         self.graphs.clear()
 
 
-def stage_state(ws, sched, B: int, n: int, solver=None, eng=None, max_states: int = 8, hw: int = None, objective: str = 'noise') -> StageState:
+def stage_state(ws, sched, B: int, n: int, solver=None, eng=None, max_states: int = 8, hw: int = None, objective: str = 'noise',
+                start: int = 0) -> StageState:
     """The workspace's state for this schedule / solver setting, keyed by T for the default call and (T, S, sampler, eta) otherwise; an
     inpainting call (``hw``) has its own: that key plus an 'inpaint' marker, bounded together with the solver states.  An ``objective`` other
-    than 'noise' (another coefficient table) is appended to the key in the same way; the keys of a noise-predicting U-Net are what they were."""
+    than 'noise' (another coefficient table) is appended to the key in the same way; the keys of a noise-predicting U-Net are what they were.
+    ``start`` > 0 (a loop that skips its first steps: an init image) is part of the key for 'dpmpp_2m' only, whose table depends on it."""
     store = ws.sampler_state
     key = sched.num_timesteps if solver is None else (sched.num_timesteps,) + tuple(solver)
+    if not (start and solver is not None and solver[1] == 'dpmpp_2m'):
+        start = 0
+    if start:
+        key = key + (("start", start),)
     if objective != 'noise':
         key = (key if isinstance(key, tuple) else (key,)) + (objective,)
     if hw is not None:
@@ -182,14 +201,16 @@ def stage_state(ws, sched, B: int, n: int, solver=None, eng=None, max_states: in
             if eng is not None:
                 eng.drop_step_tables(ws, old.t_state)
     if st is None:
-        st = store[key] = StageState(sched, B, n, ws.dev, solver, hw, objective)
+        st = store[key] = StageState(sched, B, n, ws.dev, solver, hw, objective, start)
     return st
 
 
-def known_begin(st: StageState, ws, shape, inpaint, *, sched, known_noise, seed: int, sample0: int, stage: int, stream):
+def known_begin(st: StageState, ws, shape, inpaint, *, sched, known_noise, seed: int, sample0: int, stage: int, stream, start: int = 0, steps: int = None):
     """The known region of an inpainting call at this stage: the caller's images resized to the stage's size (cubic taps), clamped to [0, 1]
     and normalised INTO st.known, the masks resized (nearest) into st.mask, and blend 0 on the x_T just drawn: the known pixels at the noise
-    level of x_T.  ``inpaint`` = (images float32 [B, C, H, W], masks uint8 [B, Hm, Wm], normalize), on the device."""
+    level of x_T.  ``inpaint`` = (images float32 [B, C, H, W], masks uint8 [B, Hm, Wm], normalize), on the device.
+    ``start`` = a0 > 0 (the loop of ``steps`` steps begins at step a0 on an init-noised x): blend 0 at THAT level, with the known-region draw
+    a0 -- the one the tail of step a0 - 1 would have used -- through a copy of the block whose stream and buffer are moved on by a0."""
     lib = L.lib()
     images, masks, normalize = inpaint
     B, Cc, H, W = shape
@@ -199,36 +220,64 @@ def known_begin(st: StageState, ws, shape, inpaint, *, sched, known_noise, seed:
                                        L.ptr(st.mask), H, stream), "mi_inpaint_prepare_fwd")
     st.known_noise = known_noise          # (st.ip holds its address: an injected buffer lives until the next call's)
     st.ip = L.MiInpaintParams(L.ptr(st.known), L.ptr(st.mask), H * W, (stage << 20) | (3 << 18), L.ptr(known_noise))
-    a, b = sched.known_start_coefs()
-    L.check(lib.mi_inpaint_blend0_fwd(L.ptr(ws.x), B, n, C.byref(st.ip), a, b, int(seed) & 0x7FFFFFFFFFFFFFFF, sample0, stream), "mi_inpaint_blend0_fwd")
+    ip0 = st.ip
+    if start:
+        a, b = sched.init_start_coefs(steps, start)
+        ip0 = L.MiInpaintParams.from_buffer_copy(st.ip)
+        ip0.known_stream += start
+        if known_noise is not None:
+            ip0.known_noise = L.ptr(known_noise) + start * B * n * 4
+    else:
+        a, b = sched.known_start_coefs()
+    L.check(lib.mi_inpaint_blend0_fwd(L.ptr(ws.x), B, n, C.byref(ip0), a, b, int(seed) & 0x7FFFFFFFFFFFFFFF, sample0, stream), "mi_inpaint_blend0_fwd")
 
 
 def stage_begin(unet, shape, *, noise_scheduler, ws, noise_fn=None, seed: int = 0, sample0: int = 0, stage: int = 0, solver=None, max_states: int = 8,
-                inpaint=None, objective: str = 'noise'):
+                inpaint=None, objective: str = 'noise', start: int = 0, init=None):
     """Everything of a stage's loop that does not depend on the PREVIOUS stage's image: x_T (Imagen.py:400), the device-resident timestep, the
     per-step conditioning tables of all T steps -- and, for an inpainting call (``inpaint``: see known_begin), the stage's known image and mask
     and blend 0.  sample() issues it for every stage before the first stage's loop, so that a later stage's
     stream has it done while it waits for its low-resolution input (on-device noise only: injected noise is drawn in the reference's order,
-    then the T known-region draws)."""
+    then the T known-region draws).
+    ``init`` = (images float32 [B, C, H, W] on the device, normalize) with ``start`` = a0: the loop begins at step a0 on
+    x = a y' + b eps -- y' the images at the stage's size in the sampler's range, (a, b) the level of the first executed step
+    (init_start_coefs), eps the stage's OWN x_T draw (same Philox stream and keying, or the same noise_fn call), made by ONE launch
+    (mi_init_noise_fwd) in place of the x_T fill; every other draw keeps its index, the device step index becomes T - 1 - a0."""
     lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
     B, n = shape[0], shape[1] * shape[2] * shape[3]
     T = noise_scheduler.num_timesteps if solver is None else solver[0]        # steps of the loop (one draw each, for every solver)
-    st = stage_state(ws, noise_scheduler, B, n, solver, eng, max_states, hw=None if inpaint is None else shape[2] * shape[3], objective=objective)
+    assert 0 <= start < T and (init is not None or not start), (start, T)
+    st = stage_state(ws, noise_scheduler, B, n, solver, eng, max_states, hw=None if inpaint is None else shape[2] * shape[3], objective=objective,
+                     start=start)
     noise_dev = known_noise = None
+    x_t_stream = (stage << 20) | (1 << 19) | 1
+
+    def init_noise(eps):                                                     # x = a y' + b eps (eps None: the x_T draw, generated in the launch)
+        at_size = cubic_resize(ws, init[0], shape[2], stream)
+        a, b = noise_scheduler.init_start_coefs(None if solver is None else T, start)
+        L.check(lib.mi_init_noise_fwd(L.ptr(at_size), L.ptr(ws.x), B, n, 1 if init[1] else 0, a, b, seed, sample0, x_t_stream, L.ptr(eps), stream),
+                "mi_init_noise_fwd")
+
     if noise_fn is not None:
-        ws.x.copy_(noise_fn(shape))                                          # Imagen.py:400
+        if init is None:
+            ws.x.copy_(noise_fn(shape))                                      # Imagen.py:400
+        else:
+            init_noise(noise_fn(shape).to(ws.dev, torch.float32).contiguous())
         noise_dev = torch.stack([noise_fn(shape) for _ in range(T)]).to(ws.dev).contiguous()   # Imagen.py:361, in step order
         if inpaint is not None:
             known_noise = torch.stack([noise_fn(shape) for _ in range(T)]).to(ws.dev).contiguous()   # blends 0 .. T-1
+    elif init is None:
+        L.check(lib.mi_randn_fill(L.ptr(ws.x), B, n, seed, sample0, x_t_stream, stream), "mi_randn_fill")
     else:
-        L.check(lib.mi_randn_fill(L.ptr(ws.x), B, n, seed, sample0, (stage << 20) | (1 << 19) | 1, stream), "mi_randn_fill")
+        init_noise(None)
     if inpaint is not None:
-        known_begin(st, ws, shape, inpaint, sched=noise_scheduler, known_noise=known_noise, seed=seed, sample0=sample0, stage=stage, stream=stream)
+        known_begin(st, ws, shape, inpaint, sched=noise_scheduler, known_noise=known_noise, seed=seed, sample0=sample0, stage=stage, stream=stream,
+                    start=start, steps=None if solver is None else T)
     if st.t_map is None:
-        L.check(lib.mi_step_set(L.ptr(st.t_state), L.ptr(ws.times), B, T - 1, stream), "mi_step_set")
+        L.check(lib.mi_step_set(L.ptr(st.t_state), L.ptr(ws.times), B, T - 1 - start, stream), "mi_step_set")
     else:
         # the device-resident state is the STEP index; the U-Net's conditioning sees the trained timestep t_map[step]
-        L.check(lib.mi_step_set_mapped(L.ptr(st.t_state), L.ptr(ws.times), B, T - 1, C.byref(st.ext), stream), "mi_step_set_mapped")
+        L.check(lib.mi_step_set_mapped(L.ptr(st.t_state), L.ptr(ws.times), B, T - 1 - start, C.byref(st.ext), stream), "mi_step_set_mapped")
     if st.x0_prev is not None:
         st.x0_prev.zero_()                                       # the first step's history coefficient is 0: 0 * stale must not be NaN
     eng.prepare_step_tables(ws, T, st.t_state, stream, t_map=st.tau)         # (timestep, text)-only conditioning of all T steps, once
@@ -236,14 +285,16 @@ def stage_begin(unet, shape, *, noise_scheduler, ws, noise_fn=None, seed: int = 
 
 
 def stage_attach(unet, shape, *, noise_scheduler, ws, first: StageState, stage: int = 0, solver=None, max_states: int = 8, inpaint=None,
-                 objective: str = 'noise') -> StageState:
+                 objective: str = 'noise', start: int = 0) -> StageState:
     """The state of a FURTHER workspace a stage visits in this call (a guidance plan of several runs), behind stage_begin on
     the first one: its step tables, and for an inpainting call its known image and mask, copied from ``first`` (resized once) over the same
-    known-region noise.  No draw: x, the history and the step index arrive with the hand-over (stage_handover)."""
+    known-region noise.  No draw: x, the history and the step index arrive with the hand-over (stage_handover).  ``start``: as stage_begin's
+    (it selects the state: the table of a 'dpmpp_2m' loop that skips its first steps)."""
     eng = unet.engine()
     B, n = shape[0], shape[1] * shape[2] * shape[3]
     T = noise_scheduler.num_timesteps if solver is None else solver[0]
-    st = stage_state(ws, noise_scheduler, B, n, solver, eng, max_states, hw=None if inpaint is None else shape[2] * shape[3], objective=objective)
+    st = stage_state(ws, noise_scheduler, B, n, solver, eng, max_states, hw=None if inpaint is None else shape[2] * shape[3], objective=objective,
+                     start=start)
     if inpaint is not None:
         st.known.copy_(first.known)
         st.mask.copy_(first.mask)
@@ -307,7 +358,7 @@ def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream):
 
 def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, noise_fn=None, seed: int = 0, sample0: int = 0,
                   stage: int = 0, use_graph: bool = True, begun=None, solver=None, group_max: int = 8, max_states: int = 8, inpaint=None,
-                  objective: str = 'noise', rescale: float = 0., steps=None, scale_tab=None, finalize: bool = True):
+                  objective: str = 'noise', rescale: float = 0., steps=None, scale_tab=None, finalize: bool = True, init=None):
     """Imagen.py:373-420 + :329-370 + :261-326: T replays of [U-Net (both guidance halves) -> CFG combine + x0 -> dynamic-threshold quantile ->
     posterior draw -> t -= 1].  ``solver`` = (S, sampler, eta): S steps over a subsequence of the trained timesteps; the loop, the noise index and the
     Philox stream count STEPS: the reference's loop with T = S but for the state's step -> timestep map and history buffer (``st.ext``).
@@ -318,7 +369,9 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
     the state's step index is T - 1 - a on entry: stage_begin or stage_handover put it there) and, with ``finalize=False``, returns None
     instead of the image.  ``scale_tab`` (host float [T] or [T, B] in execution order; on a workspace built with fold=False): the run reads its
     scale per step and row from the state's ``scale_tab`` -- mi_cfg_sched_combine_fwd, or the sched forms of the two rescale launches,
-    between the U-Net and the tail."""
+    between the U-Net and the tail.
+    ``init`` (see stage_begin): the loop starts from an init image at step a = ``steps``[0] -- it only matters when the
+    stage has not begun yet (``begun`` None: injected noise), the run itself is a run (a, T) like any other."""
     lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
     B, Cc, H, W = shape
     n = Cc * H * W
@@ -332,7 +385,7 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
     combine = two and ws.cfg_fold is None and not rescale and not sched   # guidance folded into the U-Net's tail / rescaled / combined in place: ws.pred holds B guided rows
     if begun is None:
         begun = stage_begin(unet, shape, noise_scheduler=noise_scheduler, ws=ws, noise_fn=noise_fn, seed=seed, sample0=sample0, stage=stage, solver=solver, max_states=max_states,
-                            inpaint=inpaint, objective=objective)
+                            inpaint=inpaint, objective=objective, **({} if init is None else dict(init=init, start=0 if steps is None else steps[0])))
     st, noise_dev = begun
     a_step, b_step = (0, T) if steps is None else steps
     assert 0 <= a_step < b_step <= T, steps

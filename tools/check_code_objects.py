@@ -17,7 +17,8 @@ READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 DEFAULT_PATH = (r"conv_stripe_kernel", r"cross_attn_f16x3_kernelILi(8|16)E", r"cross_attn_cond_f16x3_kernel", r"attn_cond_rows_kernel", r"crossembed_mfma_kernel", r"init_down_mfma_kernel", r"sampler_small_kernel", r"sampler_group_kernel", r"cfg_x0_kernel",
                 r"posterior_kernel", r"quantile_hist_kernel", r"quantile_finish_kernel", r"cond_step_kernel", r"text_cond_kernel", r"attn_fold_rows_kernel",
                 r"conv_rp_kernelINS_5RpCfgILi8ELi(64|32)ELi[12]ELb[01]ELb0E(Li0ELi[1-4]ELi[0-4]|Li1ELi[12]ELi0|Li2ELi1ELi0)ELb0E",      # k3 s1 | nearest x2 | k4 s2 (8 input channels)
-                r"cfg_rescale_(stats|apply)_kernel", r"cfg_sched_combine_kernel")      # the guidance launches between the U-Net and the tail (scalar and table forms)
+                r"cfg_rescale_(stats|apply)_kernel", r"cfg_sched_combine_kernel",      # the guidance launches between the U-Net and the tail (scalar and table forms)
+                r"init_noise_kernel")                                                  # the starting point of a loop that begins at an init image
 
 
 def kernel_scratch(code_object: str):
