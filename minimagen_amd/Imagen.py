@@ -10,11 +10,13 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib as L
+from . import sample_call
 from . import sampler as S
 from . import train_ops
 from .Unet import Unet
 from .diffusion_model import GaussianDiffusion
-from .helpers import (cast_tuple, default, eval_decorator, exists, module_device, normalize_neg_one_to_one, resize_image_to)
+from .helpers import (cast_tuple, default, eval_decorator, exists, module_device, normalize_neg_one_to_one, null_context, resize_image_to)
+from .sample_call import SampleCall, StageCall
 from .t5 import get_encoded_dim, t5_encode_text
 
 # the sampler tail of images too large for one workgroup (the super-resolution stages) as ONE launch of cooperating workgroups
@@ -32,7 +34,7 @@ SAMPLE_LANES = max(1, int(os.environ.get("MINIMAGEN_SAMPLE_LANES", "2")))     # 
 # 1: a synchronous sample() waits on the HOST for its last stage and checks the cooperative kernels' status words before it returns (the
 # default defers the check to the next API entry: the failed call's images are NaN -- fail-stop -- so nothing plausible-but-wrong escapes)
 STRICT_STATUS = os.environ.get("MINIMAGEN_STRICT_STATUS", "0") != "0"
-_STAGE_STREAMS = {}          # (device, lanes, stages, priority mode) -> [lane][stage] HIP streams, process-wide (see sample())
+_STAGE_STREAMS = {}          # (device, lanes, stages, priority mode) -> [lane][stage] HIP streams, process-wide (see Imagen._call_streams)
 
 
 class Imagen(nn.Module):
@@ -70,18 +72,15 @@ class Imagen(nn.Module):
         num_unets = len(unets)
 
         def per_unet(val, name, ok, what):
-            vals = tuple(val) if isinstance(val, (list, tuple)) else (val,) * num_unets      # (the parameter JSON turns tuples into lists)
-            if len(vals) != num_unets:
-                raise ValueError(f"{name} needs one value per U-Net ({num_unets}), got {len(vals)}")
+            vals = tuple(sample_call.per_stage(val, num_unets, name, unit="U-Net"))
             for v in vals:
-                if not ok(v):
-                    raise ValueError(f"{name} must be {what}, got {v!r}")
+                sample_call.reject(not ok(v), f"{name} must be {what}, got {v!r}")
             return vals
         self.pred_objectives = per_unet(pred_objectives, "pred_objectives", lambda v: isinstance(v, str) and v in GaussianDiffusion.OBJECTIVES,
                                         f"one of {GaussianDiffusion.OBJECTIVES}")
         self.min_snr_loss_weight = per_unet(min_snr_loss_weight, "min_snr_loss_weight", lambda v: isinstance(v, bool), "a bool")
         self.min_snr_gamma = tuple(float(v) for v in per_unet(
-            min_snr_gamma, "min_snr_gamma", lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and v > 0. and v == v, "a positive number"))
+            min_snr_gamma, "min_snr_gamma", lambda v: sample_call.is_number(v) and v > 0. and v == v, "a positive number"))
         self._loss_weights = {}                  # (U-Net index, device) -> the fp32 weight table of that U-Net's min-SNR setting, where the loss reads it
         self.noise_schedulers = nn.ModuleList([GaussianDiffusion(timesteps=t) for t in cast_tuple(timesteps, num_unets)])
         # built from the RAW argument like Imagen.py:78 (so only an int works, as in the reference)
@@ -202,230 +201,18 @@ class Imagen(nn.Module):
         return self._p_losses(unet, images, times, text_embeds=text_embeds, text_mask=text_masks, noise_scheduler=noise_scheduler,
                               lowres_cond_img=lowres_cond_img, lowres_aug_times=lowres_aug_times, unet_index=k)
 
-    # ------------------------------------------------------------------ sampling
     # ------------------------------------------------------------------ sampling (the loop itself: minimagen_amd/sampler.py)
-    def _stage_state(self, ws, sched: GaussianDiffusion, B: int, n: int, solver=None, eng=None):
-        return S.stage_state(ws, sched, B, n, solver, eng, MAX_SOLVER_STATES)
+    def _stage_state(self, ws, sched: GaussianDiffusion, shape, call: StageCall, eng=None):
+        return S.stage_state(ws, sched, shape, call, eng, MAX_SOLVER_STATES)
 
-    def _stage_begin(self, unet: Unet, shape, **kw):          # -> (stage state, injected noise)
-        return S.stage_begin(unet, shape, max_states=MAX_SOLVER_STATES, **kw)
+    def _stage_begin(self, unet: Unet, shape, ws, call: StageCall, **kw):          # -> (stage state, injected noise)
+        return S.stage_begin(unet, shape, ws, call, max_states=MAX_SOLVER_STATES, **kw)
 
-    def _p_sample_loop(self, unet: Unet, shape, **kw):        # Imagen.py:373-420 -> the stage's image
-        return S.p_sample_loop(self, unet, shape, group_max=SAMPLER_GROUP_MAX if SAMPLER_GROUP else 0, max_states=MAX_SOLVER_STATES, **kw)
+    def _p_sample_loop(self, unet: Unet, shape, ws, call: StageCall, run=None, **kw):        # Imagen.py:373-420 -> the stage's image
+        return S.p_sample_loop(self, unet, shape, ws, call, run, group_max=SAMPLER_GROUP_MAX if SAMPLER_GROUP else 0, max_states=MAX_SOLVER_STATES, **kw)
 
-    def _parse_solver(self, sample_steps, sampler, sampler_eta):
-        """Per stage: None (the reference's loop on all T timesteps) or (S, sampler, eta).  Host only; raises ValueError on bad values."""
-        n_stages = len(self.unets)
-        if sampler is not None and sampler not in GaussianDiffusion.SAMPLERS:
-            raise ValueError(f"sampler must be one of {GaussianDiffusion.SAMPLERS}, got {sampler!r}")
-        name = default(sampler, 'ddpm')
-        if sampler_eta is not None:
-            if name != 'ddim':
-                raise ValueError("sampler_eta goes with sampler='ddim' only")
-            if isinstance(sampler_eta, bool) or not isinstance(sampler_eta, (int, float)) or not 0. <= float(sampler_eta) <= 1.:
-                raise ValueError(f"sampler_eta must be a number in [0, 1], got {sampler_eta!r}")
-        eta = {'ddpm': 1., 'ddim': float(default(sampler_eta, 0.)), 'dpmpp_2m': 0.}[name]
-        if isinstance(sample_steps, (list, tuple)):
-            steps = tuple(sample_steps)
-            if len(steps) != n_stages:
-                raise ValueError(f"sample_steps needs one value per stage ({n_stages}), got {len(steps)}")
-        else:
-            steps = (sample_steps,) * n_stages
-        out = []
-        for S, sched in zip(steps, self.noise_schedulers):
-            T = sched.num_timesteps
-            if S is None:
-                S = T
-            if isinstance(S, bool) or not isinstance(S, int) or not 2 <= S <= T:
-                raise ValueError(f"sample_steps must be an int in [2, {T}] for a stage trained with {T} timesteps, got {S!r}")
-            out.append(None if (S == T and name == 'ddpm') else (S, name, eta))
-        return out
-
-    def _parse_inpaint(self, batch_size: int, inpaint_images, inpaint_masks, start_image, start_at_stage, stop_at_stage):
-        """-> (first stage, one past the last stage, (images float32 [B, C, H, W], masks uint8 [B, Hm, Wm]) or None, start image float32 or None),
-        the tensors still where the caller has them.  Host only; raises ValueError on bad or inconsistent values."""
-        n_stages = len(self.unets)
-
-        def stage_index(v, name, lo, hi):
-            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
-                raise ValueError(f"{name} must be an int in [{lo}, {hi}] for a cascade of {n_stages} stages, got {v!r}")
-            return v
-
-        def images(t, name):
-            if not torch.is_tensor(t) or t.dim() != 4 or not t.is_floating_point():
-                raise ValueError(f"{name} must be a float tensor [B, {self.channels}, H, W]")
-            if t.shape[0] != batch_size:
-                raise ValueError(f"{name}: batch {t.shape[0]} does not match the text batch {batch_size}")
-            if t.shape[1] != self.channels:
-                raise ValueError(f"{name}: {t.shape[1]} channels, the model has {self.channels}")
-            if t.shape[2] != t.shape[3] or t.shape[2] < 1:
-                raise ValueError(f"{name} must be square, got {tuple(t.shape[2:])}")
-            return t.detach().to(torch.float32)
-
-        stop = n_stages if stop_at_stage is None else stage_index(stop_at_stage, "stop_at_stage", 1, n_stages)
-        start = 0
-        if (start_image is None) != (start_at_stage is None):
-            raise ValueError("start_image and start_at_stage go together")
-        if start_at_stage is not None:
-            start = stage_index(start_at_stage, "start_at_stage", 1, n_stages - 1)
-            if start >= stop:
-                raise ValueError(f"start_at_stage = {start} must be below stop_at_stage = {stop}")
-            if not self.unets[start].lowres_cond:
-                raise ValueError(f"stage {start} takes no low-resolution conditioning image: it cannot start from one")
-            start_image = images(start_image, "start_image")
-        inpaint = None
-        if (inpaint_images is None) != (inpaint_masks is None):
-            raise ValueError("inpaint_images and inpaint_masks go together")
-        if inpaint_images is not None:
-            inpaint_images = images(inpaint_images, "inpaint_images")
-            m = inpaint_masks
-            if not torch.is_tensor(m) or m.dim() not in (3, 4) or (m.dim() == 4 and m.shape[1] != 1):
-                raise ValueError("inpaint_masks must be a tensor [B, H, W] or [B, 1, H, W]")
-            if m.shape[0] != batch_size:
-                raise ValueError(f"inpaint_masks: batch {m.shape[0]} does not match the text batch {batch_size}")
-            m = m.detach().reshape(m.shape[0], m.shape[-2], m.shape[-1])
-            if m.shape[1] < 1 or m.shape[2] < 1:
-                raise ValueError("inpaint_masks: empty")
-            if m.dtype != torch.bool and not bool(((m == 0) | (m == 1)).all()):
-                raise ValueError("inpaint_masks must hold 0 / 1 (or be bool)")
-            inpaint = (inpaint_images, m.to(torch.uint8))
-        return start, stop, inpaint, start_image
-
-    def _parse_init(self, batch_size: int, init_images, init_strength, solvers, first_stage: int, end_stage: int):
-        """-> (init images float32 [B, C, H, W] still where the caller has them, or None; per stage None -- the stage starts from pure noise -- or
-        a0, the number of loop steps it skips: sampler.init_start_step).  A strength for a stage the call does not run is ignored.  Host only;
-        raises ValueError on bad or inconsistent values."""
-        n_stages = len(self.unets)
-        if init_images is None and init_strength is None:
-            return None, [None] * n_stages
-        if init_images is None or init_strength is None:
-            raise ValueError("init_images and init_strength go together")
-        t = init_images
-        if not torch.is_tensor(t) or t.dim() != 4 or not t.is_floating_point():
-            raise ValueError(f"init_images must be a float tensor [B, {self.channels}, H, W]")
-        if t.shape[0] != batch_size:
-            raise ValueError(f"init_images: batch {t.shape[0]} does not match the text batch {batch_size}")
-        if t.shape[1] != self.channels:
-            raise ValueError(f"init_images: {t.shape[1]} channels, the model has {self.channels}")
-        if t.shape[2] != t.shape[3] or t.shape[2] < 1:
-            raise ValueError(f"init_images must be square, got {tuple(t.shape[2:])}")
-        if isinstance(init_strength, (list, tuple)):
-            strengths = list(init_strength)
-            if len(strengths) != n_stages:
-                raise ValueError(f"init_strength needs one entry per stage ({n_stages}), got {len(strengths)}")
-        else:
-            if init_strength is None or isinstance(init_strength, bool) or not isinstance(init_strength, (int, float)):
-                raise ValueError(f"init_strength must be a number in (0, 1] or a list with a number or None per stage, got {init_strength!r}")
-            strengths = [init_strength] * n_stages
-        starts = [None] * n_stages
-        for stage, v in enumerate(strengths):
-            if v is None:
-                continue
-            n_steps = self.noise_schedulers[stage].num_timesteps if solvers[stage] is None else solvers[stage][0]
-            a0 = S.init_start_step(n_steps, v)                   # (validates the value of every entry, run or not)
-            if first_stage <= stage < end_stage:
-                starts[stage] = a0
-        if all(a0 is None for a0 in starts):
-            raise ValueError("init_strength: every stage the call runs has None")
-        return t.detach().to(torch.float32), starts
-
-    def _parse_guidance(self, batch_size: int, cond_scale, texts, text_embeds, text_masks, negative_texts, negative_text_embeds,
-                        negative_text_masks, guidance_rescale, guided: bool = None):
-        """``guided``: whether any step of the call is guided (None: ``cond_scale`` != 1, a call without a guidance schedule).
-        -> (phi: 0. when off, negative captions: None, a list of ``batch_size`` strings, or (embeds, mask or None) still where the caller has
-        them).  Host only; raises ValueError on bad or inconsistent values."""
-        phi = 0.
-        if guidance_rescale is not None:
-            if isinstance(guidance_rescale, bool) or not isinstance(guidance_rescale, (int, float)) or not 0. <= float(guidance_rescale) <= 1.:
-                raise ValueError(f"guidance_rescale must be a number in [0, 1], got {guidance_rescale!r}")
-            phi = float(guidance_rescale)
-        negative = None
-        if negative_texts is not None and negative_text_embeds is not None:
-            raise ValueError("pass negative_texts or negative_text_embeds, not both")
-        if negative_text_masks is not None and negative_text_embeds is None:
-            raise ValueError("negative_text_masks goes with negative_text_embeds")
-        masked = exists(text_masks) or not exists(text_embeds)              # (captions encoded here always come with masks)
-        if negative_texts is not None:
-            if isinstance(negative_texts, str):
-                negative_texts = [negative_texts] * batch_size
-            if not isinstance(negative_texts, (list, tuple)) or not all(isinstance(t, str) for t in negative_texts):
-                raise ValueError("negative_texts must be a string or a list of strings")
-            if len(negative_texts) != batch_size:
-                raise ValueError(f"negative_texts: batch {len(negative_texts)} does not match the text batch {batch_size}")
-            if not masked:
-                raise ValueError("negative_texts are encoded with masks: pass text_masks with text_embeds (the captions and the negative captions "
-                                 "must both carry masks, or neither)")
-            negative = list(negative_texts)
-        elif negative_text_embeds is not None:
-            e, m = negative_text_embeds, negative_text_masks
-            if not torch.is_tensor(e) or e.dim() != 3 or not e.is_floating_point():
-                raise ValueError("negative_text_embeds must be a float tensor [B, L, E]")
-            if e.shape[0] != batch_size:
-                raise ValueError(f"negative_text_embeds: batch {e.shape[0]} does not match the text batch {batch_size}")
-            if e.shape[2] != self.text_embed_dim:
-                raise ValueError(f"negative_text_embeds: embedding dimension {e.shape[2]}, the model has {self.text_embed_dim}")
-            if m is not None and (not torch.is_tensor(m) or tuple(m.shape) != tuple(e.shape[:2])):
-                raise ValueError(f"negative_text_masks must be a tensor {tuple(e.shape[:2])} like negative_text_embeds")
-            if masked != (m is not None):
-                raise ValueError("negative prompts: the captions and the negative captions must both carry masks, or neither")
-            if m is None and exists(text_embeds) and text_embeds.shape[1] != e.shape[1]:
-                raise ValueError(f"negative prompts: unmasked captions of different lengths ({text_embeds.shape[1]} and {e.shape[1]}) cannot be "
-                                 "joined; pass masks")
-            negative = (e.detach(), None if m is None else m.detach())
-        if (phi or negative is not None) and not (cond_scale != 1. if guided is None else guided):
-            raise ValueError("negative prompts and guidance_rescale need cond_scale != 1 (or a guidance schedule with a guided step): at 1 the second "
-                             "half of the guidance batch is never evaluated")
-        return phi, negative
-
-    def _parse_guidance_schedule(self, batch_size: int, cond_scale, solvers, guidance_interval, guidance_schedule):
-        """-> None when neither keyword is given, else per stage None (``cond_scale`` on every step, the call as it was) or that stage's guidance
-        scales, float64 [S] or [S, B] in execution order (sampler.guidance_scale_table).  Host only; raises ValueError on bad values."""
-        if guidance_interval is None and guidance_schedule is None:
-            return None
-        n_stages = len(self.unets)
-
-        def per_stage(v, name, single):
-            if single(v):
-                return [v] * n_stages
-            if not isinstance(v, (list, tuple)) or len(v) != n_stages:
-                raise ValueError(f"{name} needs one entry per stage ({n_stages})")
-            return list(v)
-
-        def number(v):
-            return not isinstance(v, bool) and isinstance(v, (int, float))
-
-        intervals = [None] * n_stages
-        if guidance_interval is not None:
-            is_pair = lambda v: isinstance(v, (list, tuple)) and len(v) == 2 and all(number(x) for x in v)
-            intervals = per_stage(guidance_interval, "guidance_interval", is_pair)
-            for iv in intervals:
-                if iv is None:
-                    continue
-                if not is_pair(iv) or not 0. <= float(iv[0]) <= float(iv[1]) <= 1.:
-                    raise ValueError(f"guidance_interval must be (lo, hi) with 0 <= lo <= hi <= 1 (or None for a stage), got {iv!r}")
-            if all(iv is None for iv in intervals):
-                raise ValueError("guidance_interval: every stage's entry is None")
-            intervals = [None if iv is None else (float(iv[0]), float(iv[1])) for iv in intervals]
-        schedules = [None] * n_stages
-        if guidance_schedule is not None:
-            if cond_scale != 1.:
-                raise ValueError("guidance_schedule is the scale itself: leave cond_scale at 1")
-            schedules = per_stage(guidance_schedule, "guidance_schedule", callable)
-            if all(s is None for s in schedules):
-                raise ValueError("guidance_schedule: every stage's entry is None")
-        elif cond_scale == 1.:
-            raise ValueError("guidance_interval needs cond_scale != 1 (or a guidance_schedule): outside the interval the scale is 1 already")
-        if isinstance(cond_scale, bool) or not isinstance(cond_scale, (int, float)) or cond_scale != cond_scale or abs(cond_scale) == float("inf"):
-            raise ValueError(f"cond_scale must be a finite number, got {cond_scale!r}")
-        tables = []
-        for stage, sched in enumerate(self.noise_schedulers):
-            if intervals[stage] is None and schedules[stage] is None:
-                tables.append(None)
-                continue
-            T = sched.num_timesteps
-            tau = torch.arange(T) if solvers[stage] is None else sched.sampling_timestep_map(solvers[stage][0])
-            tables.append(S.guidance_scale_table(tau, T, batch_size, cond_scale, intervals[stage], schedules[stage]))
-        return tables
+    _parse_solver, _parse_inpaint, _parse_init = sample_call.parse_solver, sample_call.parse_inpaint, sample_call.parse_init         # (host: sample_call.py)
+    _parse_guidance, _parse_guidance_schedule = sample_call.parse_guidance, sample_call.parse_guidance_schedule
 
     def _lowres_conditioning(self, unet: Unet, img, image_size: int, ws, lowres_noise_level: float, noise_fn, seed, sample0, stage):
         """Imagen.py:479-485 + :393: cubic resize (reflect pad) -> q_sample at int(T*level) -> *2-1."""
@@ -452,7 +239,7 @@ class Imagen(nn.Module):
     def sample(self, texts: List[str] = None, text_masks: torch.Tensor = None, text_embeds: torch.Tensor = None,
                cond_scale: float = 1., lowres_sample_noise_level: float = None, return_pil_images: bool = False,
                device: torch.device = None, *, _noise: Callable = None, _seed: int = 1234, _sample_offset: int = 0,
-               _use_graph: bool = True, _precision: str = None, _async: bool = False, _revalidated: bool = False,
+               _use_graph: bool = True, _precision: str = None, _async: bool = False,
                sample_steps: Union[int, List[int], Tuple[int, ...]] = None, sampler: str = None, sampler_eta: float = None,
                inpaint_images: torch.Tensor = None, inpaint_masks: torch.Tensor = None, start_image: torch.Tensor = None,
                start_at_stage: int = None, stop_at_stage: int = None,
@@ -469,9 +256,8 @@ class Imagen(nn.Module):
         Sampling in fewer steps (keyword-only, not in the reference): ``sample_steps`` = S, an int or one int per stage, 2 <= S <= T of
         that stage's schedule (None: T) walks S of the trained timesteps, tau_k = round(k (T-1) / (S-1)), one U-Net evaluation each.
         ``sampler`` = 'ddpm' (default: the reference's ancestral step on the subsequence), 'ddim' (eta = ``sampler_eta``, default 0) or
-        'dpmpp_2m' (DPM-Solver++ 2M on the thresholded x0, deterministic); ``sampler_eta`` in [0, 1] goes with 'ddim' only.  A call with
-        none of them, or with S = T and 'ddpm', IS the reference's loop (same tables, graphs and kernels as before these arguments
-        existed).  Tables: GaussianDiffusion.sampler_tables.  Bad values raise ValueError before anything is launched.
+        'dpmpp_2m' (DPM-Solver++ 2M on the thresholded x0, deterministic); ``sampler_eta`` in [0, 1] goes with 'ddim' only.  S = T with
+        'ddpm' IS the reference's loop.  Tables: GaussianDiffusion.sampler_tables.
 
         Conditioning on pixels the caller has (keyword-only, not in the reference).  ``inpaint_images`` ([B, C, H, W]
         float in [0, 1], square, any size) with ``inpaint_masks`` ([B, H, W] or [B, 1, H, W], bool or 0/1, nonzero = "known, keep"): every
@@ -480,8 +266,7 @@ class Imagen(nn.Module):
         images carry them.  One pass per step: no RePaint resampling.  ``start_image`` ([B, C, H, W] in [0, 1], square, any size) with
         ``start_at_stage`` = s >= 1 skips the stages below s and stands in for the output of stage s - 1 (run only the super-resolution
         stage on an image of the caller's); ``stop_at_stage`` = s runs the stages below s and returns that stage's image.  The noise is
-        keyed by the stage INDEX, so a cascade cut in two this way gives the bits of the whole.  A call with none of these goes through
-        exactly the states, tables, graphs and kernels it went through before they existed.
+        keyed by the stage INDEX, so a cascade cut in two this way gives the bits of the whole.
 
         A stage whose U-Net was built with ``pred_objectives`` 'v' or 'x_start' samples from a coefficient table whose columns 0 and 1 turn
         that prediction into x0 (GaussianDiffusion.sampler_coef_table), for every setting above; nothing else differs, and a 'noise' stage is
@@ -494,9 +279,8 @@ class Imagen(nn.Module):
         both sides carry masks (the shorter is padded with zero embeddings under a False mask); both sides masked, or neither.
         ``guidance_rescale`` = phi in [0, 1] (Lin et al. 2023; None and 0: off): per image, the guided prediction g is scaled to the standard
         deviation of the conditional prediction c and mixed with itself, g * (phi * std(c) / std(g) + 1 - phi), on what the U-Net predicts
-        (whatever its objective), before x0 and the dynamic threshold.  Both go with every setting above.  Bad values raise ValueError
-        before anything is launched; a call with neither goes through exactly the workspaces, states, graphs and kernels it went through
-        before they existed.  Nothing here has been tried on a trained model: what is checked is the arithmetic.
+        (whatever its objective), before x0 and the dynamic threshold.  Both go with every setting above.  Nothing here has been tried on a
+        trained model: what is checked is the arithmetic.
 
         Guidance over the steps (keyword-only, not in the reference).  ``guidance_interval`` = (lo, hi), 0 <= lo <= hi <= 1,
         one pair for every stage or a list with a pair or None per stage (needs ``cond_scale`` != 1 or a schedule): the step at trained
@@ -507,248 +291,167 @@ class Imagen(nn.Module):
         A step whose scales are all exactly 1 is unguided (negative prompts and ``guidance_rescale``, the identity there, are skipped; they
         need one guided step somewhere).  A stage moves between its B-row and its 2 B-row workspace at the run boundaries (x, the
         dpmpp_2m history and the step index are handed over; same noise stream); an interval of (0, 1), a constant schedule s or an
-        all-ones schedule IS the call with ``cond_scale`` = s / 1.  Bad values, lengths and shapes raise ValueError before anything is launched.
+        all-ones schedule IS the call with ``cond_scale`` = s / 1.
 
         Starting from an image (SDEdit / "img2img"; keyword-only, not in the reference).  ``init_images`` ([B, C, H, W]
         float in [0, 1], square, any size; resized per stage like ``inpaint_images``) with ``init_strength`` = s in (0, 1] for every stage, or
         a list with s or None (that stage starts from pure noise, as without the keywords) per stage: a stage of S loop steps skips its
-        first a0 = S - m, m = min(S, max(1, floor(s S + 0.5))) (sampler.init_start_step), and runs the other m from
+        first a0 = S - m, m = min(S, max(1, floor(s S + 0.5))) (sample_call.init_start_step), and runs the other m from
         x = sqrt(abar_tau) y' + sqrt(1 - abar_tau) eps at tau = the trained timestep of step a0 (GaussianDiffusion.init_start_coefs) -- eps IS
         the stage's own x_T draw and every other draw keeps its index in the full loop, so a sharded batch reproduces the unsharded one and
         ``_noise`` is called in the order it is called today.  With every ``sampler`` / ``sample_steps`` ('dpmpp_2m': the first executed
         step is first order), with inpainting (blend 0 at the starting level), with ``start_image`` / ``start_at_stage`` / ``stop_at_stage`` (a
         strength for a stage that does not run is ignored) and with the guidance keywords, whose intervals and schedules stay indexed by the
         step of the FULL loop ([S] / [S, B] keep their shape, entry a0 is the first one executed; "one guided step somewhere" means an
-        executed one).  One strength per stage, not per row; no RePaint resampling.  Bad values raise ValueError before anything is
-        launched; a call without the two goes through exactly the workspaces, states, tables, graph keys and launches it goes through today.
-        Nothing here has been tried on a trained model: what is checked is the arithmetic."""
-        solvers = self._parse_solver(sample_steps, sampler, sampler_eta)
-        rescale, negative, scale_tabs = 0., None, None
-        if exists(text_embeds) or exists(texts):
-            n_rows = text_embeds.shape[0] if exists(text_embeds) else len(texts)
-            first_stage, end_stage, inpaint, start_image = self._parse_inpaint(n_rows, inpaint_images, inpaint_masks, start_image, start_at_stage, stop_at_stage)
-            init_images, init_starts = self._parse_init(n_rows, init_images, init_strength, solvers, first_stage, end_stage)
-            scale_tabs = self._parse_guidance_schedule(n_rows, cond_scale, solvers, guidance_interval, guidance_schedule)
-            guided = None
-            if scale_tabs is not None:                           # (of the steps a stage executes: a loop that starts at an init image skips its first ones)
-                guided = any(cond_scale != 1. if scale_tabs[s] is None else bool((scale_tabs[s][init_starts[s] or 0:] != 1.).any())
-                             for s in range(first_stage, end_stage))
-            rescale, negative = self._parse_guidance(n_rows, cond_scale, texts, text_embeds, text_masks,
-                                                     negative_texts, negative_text_embeds, negative_text_masks, guidance_rescale, guided)
-        call_args = dict(guidance_interval=guidance_interval, guidance_schedule=guidance_schedule, negative_texts=negative_texts, negative_text_embeds=negative_text_embeds, negative_text_masks=negative_text_masks,
-                         guidance_rescale=guidance_rescale, init_images=init_images, init_strength=init_strength, inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, start_image=start_image, start_at_stage=start_at_stage,
-                         stop_at_stage=stop_at_stage, sample_steps=sample_steps, sampler=sampler, sampler_eta=sampler_eta, texts=texts, text_masks=text_masks, text_embeds=text_embeds, cond_scale=cond_scale, lowres_sample_noise_level=lowres_sample_noise_level,
-                         return_pil_images=return_pil_images, device=device, _noise=_noise, _seed=_seed, _sample_offset=_sample_offset,
-                         _use_graph=_use_graph, _precision=_precision, _async=_async)
-        device = default(device, self.device)
+        executed one).  One strength per stage, not per row; no RePaint resampling.  Nothing here has been tried on a trained model:
+        what is checked is the arithmetic.
+
+        For every keyword family: bad values, lengths and shapes raise ValueError before anything is launched (sample_call.parse), and a
+        family that is left out is a ``StageCall`` field at its default -- such a call goes through exactly the workspaces, states, tables,
+        graph keys and launches it went through before the family existed."""
+        call = sample_call.parse(self, **{k: v for k, v in locals().items() if k != "self"})
         self._poll_status()                  # a cooperative launch of an EARLIER call gave up (its images are NaN): raise here, never silently
         self._status_stages = []
-        self._reset_unets_all_one_device(device=device)
-        if exists(texts) and not exists(text_embeds):
-            text_embeds, text_masks = t5_encode_text(texts, name=self.text_encoder_name)
-            text_embeds, text_masks = map(lambda t: t.to(device), (text_embeds, text_masks))
-        assert exists(text_embeds), 'text or text encodings must be passed into Imagen'
+        call, lane, streams = self._place(call)
+        # Packed-weight validation, once per call (DESIGN.md section 4): identity up front, the content fingerprint launched and read AFTER the call's
+        # work is enqueued.  A rare positive verdict (p.data updates behind the version counters: what was enqueued ran on stale packs) discards that
+        # work and issues the SAME placed call again behind the whole check; injected noise (a stateful generator: no second run) keeps it all up front.
+        img, done, stale = self._issue(call, lane, streams, full_check=call.noise.fn is not None)
+        if stale:
+            if streams is not None:
+                torch.cuda.synchronize(img.device)
+            self._status_stages = []
+            img, done, _ = self._issue(call, lane, streams, full_check=True)
+        return self._finish(call, lane, img, done)
+
+    def _place(self, call: SampleCall):
+        """-> (the call with its captions encoded and its tensors on the device, its lane, its stage streams or None off the GPU)"""
+        self._reset_unets_all_one_device(device=call.device)
+        text_embeds, text_masks, negative = call.text_embeds, call.text_masks, call.negative
+        if call.texts is not None:
+            text_embeds, text_masks = t5_encode_text(call.texts, name=self.text_encoder_name)
         if isinstance(negative, list):
             negative = t5_encode_text(negative, name=self.text_encoder_name)
-        assert not (exists(text_embeds) and text_embeds.shape[-1] != self.text_embed_dim), \
-            f'invalid text embedding dimension being passed in (should be {self.text_embed_dim})'
-        # the runs of every stage's guidance plan, (kind, first step, one past the last, scale): ONE run over all steps for a call without
-        # a schedule or interval -- and for a table that is one row-uniform value on every step, which IS that call (sampler.guidance_plan)
-        plans = {}
-        for stage in range(first_stage, end_stage):
-            w_stage = None if scale_tabs is None else scale_tabs[stage]
-            n_steps = self.noise_schedulers[stage].num_timesteps if solvers[stage] is None else solvers[stage][0]
-            a0 = init_starts[stage] or 0                         # a stage that starts from an init image: the plan of the steps [a0, S) it executes
-            plans[stage] = [('plain' if cond_scale == 1. else 'scalar', a0, n_steps, cond_scale)] if w_stage is None else \
-                [(kind, a + a0, b + a0, scale) for kind, a, b, scale in S.guidance_plan(w_stage[a0:])]
-        any_guided = any(kind != 'plain' for runs in plans.values() for kind, *_ in runs)
-        assert not (any_guided and not self.can_classifier_guidance), \
-            'imagen was not trained with conditional dropout, and thus one cannot use classifier free guidance (cond_scale anything other than 1)'
-        batch_size = text_embeds.shape[0]
         device = next(self.parameters()).device
-        lowres_sample_noise_level = default(lowres_sample_noise_level, self.lowres_sample_noise_level)
-        keeps = {kind: torch.cat((torch.ones(batch_size, dtype=torch.bool), torch.zeros(0 if kind == 'plain' else batch_size, dtype=torch.bool)))
-                 for kind in ('plain', 'scalar', 'table')}
-        text_embeds = text_embeds.to(device)
-        text_masks = text_masks.to(device) if exists(text_masks) else None
-        if inpaint is not None:
-            inpaint = tuple(t.to(device).contiguous() for t in inpaint) + (self.auto_normalize_img,)
-        if start_image is not None:
-            start_image = start_image.to(device).contiguous()
-        if init_images is not None:
-            init_images = init_images.to(device).contiguous()
-        pixel_inputs = [t for t in (inpaint or ())[:2] + (start_image, init_images) if t is not None]
-        if negative is not None:            # read by the stage streams like the captions (record_stream below)
-            negative = tuple(None if t is None else t.to(device) for t in negative)
-            pixel_inputs += [t for t in negative if t is not None]
-        neg_text = {} if negative is None else dict(negative_embeds=negative[0], negative_mask=negative[1])
-
-        # One HIP stream PER STAGE (graphs cannot be captured on the legacy default stream anyway).  Within a call stage s + 1 waits for
-        # stage s through an event; ACROSS calls the stages form a pipeline: with ``_async=True`` the caller's stream is never made to
-        # wait, so the (small, latency-bound) base stage of call k + 1 runs on its stream while the super-resolution stage of call k
-        # still occupies the other -- each stage owns its workspace, so nothing is shared but the finished image handed down the cascade.
-        on_gpu = L.backend() == "hip-gfx950"
-        # Packed-weight validation, once per call.  Identity (pointers, version counters: host only) up front; the content fingerprint -- device
-        # work on the caller's stream + one small device -> host copy -- is launched and read AFTER this call's work is enqueued (see
-        # engine.pack_identity).  A rare positive verdict discards the enqueued work and runs the call again on fresh packs.  Injected noise
-        # (a stateful host generator: the call cannot be repeated) keeps the whole check up front.
-        for unet in self.unets:
-            if _noise is not None or _revalidated:
-                unet.engine().pack()
-            else:
-                unet.engine().pack_identity()
-        # LANES: asynchronous calls alternate between SAMPLE_LANES independent sets of (stage streams, workspaces, graphs), so that two
-        # calls are in flight side by side -- the kernels of one call's stages fill the launch floors and tails of the other's (measured:
-        # 42.8 K vs 37.7 K steps/s for the B = 32 cascade, DESIGN.md section 6).  Calls on one lane stay ordered by its streams; lanes share
-        # only read-only state (weights, tables).  Synchronous calls use lane 0.
-        lane = 0
-        if _async and on_gpu and SAMPLE_LANES > 1:
+        call = call.placed(device, text_embeds, text_masks, negative)
+        # LANES: asynchronous calls alternate between SAMPLE_LANES independent sets of (stage streams, workspaces, graphs), so that two calls are in
+        # flight side by side -- one call's kernels fill the launch floors and tails of the other's (42.8 K vs 37.7 K steps/s for the B = 32 cascade, DESIGN.md
+        # section 6).  Calls on one lane stay ordered by its streams; lanes share only read-only state (weights, tables).  Synchronous calls use lane 0.
+        lane, on_gpu = 0, L.backend() == "hip-gfx950"
+        if call.is_async and on_gpu and SAMPLE_LANES > 1:
             lane = self._lane_rr = (getattr(self, "_lane_rr", -1) + 1) % SAMPLE_LANES
+        return call, lane, self._call_streams(device, lane) if on_gpu else None
+
+    def _call_streams(self, device, lane: int):
+        """One HIP stream PER STAGE (graphs cannot be captured on the legacy default stream anyway).  Within a call stage s + 1 waits for stage s through an event;
+        ACROSS calls the stages form a pipeline: with ``_async=True`` the caller's stream is never made to wait, so the (small, latency-bound) base stage of call k +
+        1 runs on its stream while the super-resolution stage of call k still occupies the other -- each stage owns its workspace, so nothing is shared but the
+        finished image handed down the cascade."""
+        all_streams, lanes = getattr(self, "_stage_streams", None), max(1, SAMPLE_LANES)
+        if all_streams is None or len(all_streams[0]) != len(self.unets) or all_streams[0][0].device != device or len(all_streams) != lanes:
+            # earlier (smaller-image, latency-bound) stages get the higher stream priority: their short kernels then slot in between the
+            # workgroups of the later stages' large ones instead of queueing behind them
+            prio = int(os.environ.get("MINIMAGEN_STAGE_PRIORITY", "1"))
+            if all_streams is not None:
+                torch.cuda.synchronize(device)       # (rare: lane count / device changed) work queued on the old lanes' streams still owns the workspaces
+            # ONE set of stage streams per process and shape, shared by every Imagen instance.  HIP multiplexes its streams onto GPU_MAX_HW_QUEUES
+            # (default 4) hardware queues and torch hands out pool streams round robin: a second Imagen in the same process got streams whose hardware queue
+            # was shared with the stream feeding them, and every node of a graph launched there paid ~16 us (a 150 ms sample() took 261 ms;
+            # tools/gpu_realloc_slowdown.py, profiles/r04_second_instance_slowdown.txt).  The first set a process creates has never shown the sharing.
+            key = (str(device), lanes, len(self.unets), prio)
+            if key not in _STAGE_STREAMS:
+                _STAGE_STREAMS[key] = [[torch.cuda.Stream(device=device, priority=(-1 if (prio and k + 1 < len(self.unets)) else 0))
+                                        for k in range(len(self.unets))] for _ in range(lanes)]
+            self._stage_streams = all_streams = _STAGE_STREAMS[key]
+        self._stream = all_streams[0][-1]            # (benchmarks time the last stage's captured graph on its own stream)
+        return all_streams[lane]
+
+    def _issue(self, call: SampleCall, lane: int, streams, full_check: bool):
+        """Enqueue the placed call: every stage on its own stream -> (the last stage's image, its completion event or None, whether the deferred
+        weight check found the packs stale -- ``full_check``: the whole check up front instead)."""
+        for unet in self.unets:
+            unet.engine().pack() if full_check else unet.engine().pack_identity()
+        on_gpu, B, noise = streams is not None, call.batch, call.noise
+        on_stream = (lambda stage: torch.cuda.stream(streams[stage])) if on_gpu else null_context
         if on_gpu:
-            all_streams = getattr(self, "_stage_streams", None)
-            if all_streams is None or len(all_streams[0]) != len(self.unets) or all_streams[0][0].device != device or len(all_streams) != max(1, SAMPLE_LANES):
-                # earlier (smaller-image, latency-bound) stages get the higher stream priority: their short kernels then slot in between the
-                # workgroups of the later stages' large ones instead of queueing behind them
-                prio = int(os.environ.get("MINIMAGEN_STAGE_PRIORITY", "1"))
-                if all_streams is not None:
-                    torch.cuda.synchronize(device)       # (rare: lane count / device changed) work queued on the old lanes' streams still owns the workspaces
-                # ONE set of stage streams per process and shape, shared by every Imagen instance.  HIP multiplexes its streams onto
-                # GPU_MAX_HW_QUEUES (default 4) hardware queues, and torch hands out pool streams round robin: a second Imagen built in the
-                # same process got streams whose hardware queue was shared with the stream feeding them, and every node of a graph launched
-                # there paid ~16 us (2.7 ms per 170-node launch: a 150 ms sample() took 261 ms; tools/gpu_realloc_slowdown.py,
-                # profiles/r04_second_instance_slowdown.txt -- the device buffers had nothing to do with it).  The first set a process creates
-                # has never shown the sharing; keeping it for all instances makes the mapping a constant.
-                key = (str(device), max(1, SAMPLE_LANES), len(self.unets), prio)
-                all_streams = _STAGE_STREAMS.get(key)
-                if all_streams is None:
-                    all_streams = _STAGE_STREAMS[key] = [[torch.cuda.Stream(device=device, priority=(-1 if (prio and k + 1 < len(self.unets)) else 0))
-                                                          for k in range(len(self.unets))] for _ in range(max(1, SAMPLE_LANES))]
-                self._stage_streams = all_streams
-            streams = all_streams[lane]
-            self._stream = all_streams[0][-1]            # (benchmarks time the last stage's captured graph on its own stream)
-            caller_stream = torch.cuda.current_stream(device)
-            inputs_ready = caller_stream.record_event()
-        from .helpers import null_context
-        precision = _precision if _precision is not None else os.environ.get("MINIMAGEN_PRECISION", "fp32")
-        stages = list(enumerate(zip(self.unets, self.sample_channels, self.image_sizes, self.noise_schedulers)))[first_stage:end_stage]
-        known = {} if inpaint is None else dict(inpaint=inpaint)        # (a call without known pixels passes nothing new down)
-        # ... and neither does a noise-predicting stage: only another objective names itself (it selects the stage's coefficient table)
-        extras = {stage: dict(known, **({} if self.pred_objectives[stage] == 'noise' else dict(objective=self.pred_objectives[stage])),
-                              **({} if init_starts[stage] is None else dict(init=(init_images, self.auto_normalize_img))))
-                  for stage, _ in stages}
-        starts = {stage: {} if init_starts[stage] is None else dict(start=init_starts[stage]) for stage, _ in stages}
-        # guidance rescale reads both halves of the prediction: a workspace of its own that never folds the guidance into the U-Net's tail --
-        # and so does a run whose scales come from a table; an unguided run (B rows) takes neither, nor the negative captions
-        unfolded = {kind: dict(fold=False) if (kind == 'table' or (rescale and kind == 'scalar')) else {} for kind in keeps}
-        rescaled = {kind: dict(rescale=rescale) if (rescale and kind != 'plain') else {} for kind in keeps}
+            inputs_ready = torch.cuda.current_stream(call.text_embeds.device).record_event()
+        keeps = {kind: torch.cat((torch.ones(B, dtype=torch.bool), torch.zeros(0 if kind == 'plain' else B, dtype=torch.bool))) for kind in ('plain', 'scalar', 'table')}
+        negative = call.negative or (None, None)
+        lane_opts = dict(precision=call.precision, lane=lane, pipelined=bool(call.is_async and on_gpu and SAMPLE_LANES > 1))
+        t_low = int(self.lowres_noise_schedule.num_timesteps * call.lowres_noise_level)
         # ---- pass 1, every stage on its own stream: what depends on the CAPTIONS only (text conditioning, the folded context rows, x_T, the
         # step tables) -- issued for all stages up front, so a later stage has it behind it when its low-resolution input arrives
         wss, begun = {}, {}
-        for stage, (unet, channel, image_size, noise_scheduler) in stages:
+        for sc in call.stages:
+            stage, unet, size, eng = sc.stage, self.unets[sc.stage], self.image_sizes[sc.stage], self.unets[sc.stage].engine()
             if on_gpu:
                 streams[stage].wait_event(inputs_ready)
-                # the stage streams read the caller's tensors after sample() has returned (_async) / after the caller may have dropped
-                # them: tell the caching allocator, or a block freed on the caller's stream could be handed out again while a stage's
-                # text_cond launch is still queued
-                for t_in in (text_embeds, text_masks, *pixel_inputs):
-                    if t_in is not None and t_in.is_cuda:
+                # the stage streams read the caller's tensors after sample() has returned (_async) / after the caller may have dropped them: tell the
+                # caching allocator, or a block freed on the caller's stream could be handed out again while a stage's text_cond launch is still queued
+                for t_in in call.tensors:
+                    if t_in.is_cuda:
                         t_in.record_stream(streams[stage])
-            with (torch.cuda.stream(streams[stage]) if on_gpu else null_context()):
-                eng = unet.engine()
+            with on_stream(stage):
                 wss[stage] = {}
-                for kind in dict.fromkeys(run[0] for run in plans[stage]):          # every workspace the stage visits: its text, once per call
-                    # per call, never sticky engine state: a later Unet.forward stays on the engine's default precision
-                    ws = wss[stage][kind] = eng.workspace(batch_size, keeps[kind].numel(), image_size, image_size, precision=precision, lane=lane,
-                                                          pipelined=bool(_async and on_gpu and SAMPLE_LANES > 1), **unfolded[kind])
-                    eng.set_text(ws, text_embeds, text_masks, keeps[kind], **({} if kind == 'plain' else neg_text))
+                for kind in sc.kinds:                # every workspace the stage visits: its text, once per call
+                    # per call, never sticky engine state: a later Unet.forward stays on the engine's default precision.  Guidance rescale and a run whose scales come
+                    # from a table read both halves of the prediction: a workspace that never folds the guidance into the U-Net's tail; a plain run takes no negatives
+                    ws = wss[stage][kind] = eng.workspace(B, keeps[kind].numel(), size, size, fold=not (kind == 'table' or (sc.rescale and kind == 'scalar')), **lane_opts)
+                    eng.set_text(ws, call.text_embeds, call.text_masks, keeps[kind], *((None, None) if kind == 'plain' else negative))
                     if unet.lowres_cond:             # the augmentation level's timestep feeds the step tables (diffusion_model.py:68-69)
-                        ws.lowres_times.fill_(int(self.lowres_noise_schedule.num_timesteps * lowres_sample_noise_level))
-                if _noise is None:
-                    begun[stage] = self._stage_begin(unet, (batch_size, self.channels, image_size, image_size), noise_scheduler=noise_scheduler,
-                                                     ws=wss[stage][plans[stage][0][0]], seed=_seed, sample0=_sample_offset, stage=stage, solver=solvers[stage], **extras[stage], **starts[stage])
+                        ws.lowres_times.fill_(t_low)
+                if noise.fn is None:
+                    begun[stage] = self._stage_begin(unet, (B, self.channels, size, size), wss[stage][sc.kinds[0]], sc, noise_scheduler=self.noise_schedulers[stage], noise=noise)
         # ---- pass 2: the cascade
-        img, prev_done = start_image, None
-        for stage, (unet, channel, image_size, noise_scheduler) in stages:
+        img, prev_done = call.start_image, None
+        for sc in call.stages:
+            stage, unet, size = sc.stage, self.unets[sc.stage], self.image_sizes[sc.stage]
             if on_gpu and prev_done is not None:
                 streams[stage].wait_event(prev_done)
-            with (torch.cuda.stream(streams[stage]) if on_gpu else null_context()):
-                runs = plans[stage]
-                ws = wss[stage][runs[0][0]]
-                shape = (batch_size, self.channels, image_size, image_size)
+            with on_stream(stage):
+                ws, shape = wss[stage][sc.kinds[0]], (B, self.channels, size, size)
                 if unet.lowres_cond:
                     if on_gpu:
                         img.record_stream(streams[stage])
-                    self._lowres_conditioning(unet, img, image_size, ws, lowres_sample_noise_level, _noise, _seed, _sample_offset, stage)
+                    self._lowres_conditioning(unet, img, size, ws, call.lowres_noise_level, *noise, stage)
                     for other in wss[stage].values():           # drawn once, then copied
                         if other is not ws:
                             other.lowres.copy_(ws.lowres)
                             unet.engine().prepare_lowres(other)
-                loop = dict(noise_scheduler=noise_scheduler, noise_fn=_noise, seed=_seed, sample0=_sample_offset, stage=stage, use_graph=_use_graph,
-                            solver=solvers[stage], **extras[stage])
-                if len(runs) == 1 and runs[0][0] != 'table':
-                    part = {} if init_starts[stage] is None else dict(steps=runs[0][1:3])          # (a run (a0, S) of the loop, like a plan's)
-                    img = self._p_sample_loop(unet, shape, ws=ws, cond_scale=runs[0][3], begun=begun.get(stage), **loop, **rescaled[runs[0][0]], **part)
+                loop = dict(noise_scheduler=self.noise_schedulers[stage], noise=noise, use_graph=call.use_graph)
+                if len(sc.runs) == 1 and sc.runs[0][0] != 'table':
+                    img = self._p_sample_loop(unet, shape, ws, sc, begun=begun.get(stage), **loop)
                 else:
-                    img = self._run_plan(unet, shape, runs, wss[stage], scale_tabs[stage], begun.get(stage), loop, rescaled)
+                    img = S.run_plan(self, unet, shape, wss[stage], sc, begun.get(stage), max_states=MAX_SOLVER_STATES, **loop)
                 if on_gpu:
                     prev_done = streams[stage].record_event()
-        pack_tokens = [] if (_noise is not None or _revalidated) else [(unet.engine(), unet.engine().pack_begin()) for unet in self.unets]
-        if any(eng.pack_changed(tok) for eng, tok in pack_tokens):
-            # the weights' values had changed behind the version counters (p.data updates): what was enqueued ran on stale packs
-            if on_gpu:
-                torch.cuda.synchronize(device)
-            self._status_stages = []
-            call_args["_revalidated"] = True
-            return self.sample(**call_args)
+        tokens = [] if full_check else [(unet.engine(), unet.engine().pack_begin()) for unet in self.unets]
+        return img, prev_done, any(eng.pack_changed(tok) for eng, tok in tokens)
+
+    def _finish(self, call: SampleCall, lane: int, img, done):
+        """Status words, the asynchronous return, PIL images.  ``done``: the last stage's completion event (None off the GPU)."""
         if self._status_stages:
-            self._status_pending.append((prev_done, self._status_stages))
+            self._status_pending.append((done, self._status_stages))
             self._status_stages = []
-        if STRICT_STATUS and on_gpu and not _async:
-            prev_done.synchronize()
-            self._poll_status()
-        if on_gpu:
-            if _async:
-                # pipelined use: the result is ready when ``done`` is (the caller synchronises / waits on it before touching the images)
-                # per CALL: the event of this very call.  A later call on the OTHER lane does not wait for it -- capture it right after
-                # the call that produced the tensor (it also travels on the tensor), or use wait_pending_samples() to cover every lane
-                self.last_sample_done = prev_done
-                self._lane_done[lane] = prev_done
-                if not return_pil_images:
-                    img.sample_done = prev_done
+        if done is not None:
+            if STRICT_STATUS and not call.is_async:
+                done.synchronize()
+                self._poll_status()
+            if call.is_async:
+                # pipelined use: the result is ready when ``done`` is (the caller waits on it before touching the images) -- per CALL: a later call on the OTHER
+                # lane does not wait for it; capture it right after the call that produced the tensor (it travels on the tensor too), or use wait_pending_samples()
+                self.last_sample_done = self._lane_done[lane] = done
+                if not call.return_pil:
+                    img.sample_done = done
                     return img
-            caller_stream.wait_event(prev_done)              # (_async with PIL images: the device -> host copy below runs on the caller's stream)
+            caller_stream = torch.cuda.current_stream(img.device)
+            caller_stream.wait_event(done)                   # (_async with PIL images: the device -> host copy below runs on the caller's stream)
             img.record_stream(caller_stream)
-        if not return_pil_images:
+        if not call.return_pil:
             return img
         pil = _to_pil_images(img)
         self.check_device_status()
         return pil
-
-    def _run_plan(self, unet: Unet, shape, runs, workspaces, scales, begun, loop, rescaled):
-        """A stage whose guidance plan has several runs, or reads its scales from a table: every run on the workspace of
-        its kind, x / the history / the step index handed over at the run boundaries, one noise stream (``begun``: the stage_begin of the first
-        run's workspace, issued here for injected noise -- one x_T and one draw per step, whatever workspaces the stage visits) -> the image."""
-        first = workspaces[runs[0][0]]
-        begin = {k: loop[k] for k in ('noise_scheduler', 'stage', 'solver', 'inpaint', 'objective') if k in loop}
-        if 'init' in loop:                                       # the first run starts at step a0 (and selects the state of a 'dpmpp_2m' loop by it)
-            begin['start'] = runs[0][1]
-        if begun is None:
-            begun = self._stage_begin(unet, shape, ws=first, noise_fn=loop['noise_fn'], seed=loop['seed'], sample0=loop['sample0'], **begin,
-                                      **({'init': loop['init']} if 'init' in loop else {}))
-        st0, noise_dev = begun
-        states = {runs[0][0]: st0}
-        for kind, ws in workspaces.items():
-            if ws is not first:
-                states[kind] = S.stage_attach(unet, shape, ws=ws, first=st0, max_states=MAX_SOLVER_STATES, **begin)
-        n_steps = runs[-1][2]
-        img = prev = None
-        for i, (kind, a, b, scale) in enumerate(runs):
-            if prev is not None:
-                S.stage_handover(states[prev], workspaces[prev], states[kind], workspaces[kind], shape[0], n_steps - 1 - a)
-            img = self._p_sample_loop(unet, shape, ws=workspaces[kind], cond_scale=1. if kind == 'table' else scale, begun=(states[kind], noise_dev),
-                                      steps=(a, b), scale_tab=scales if kind == 'table' else None, finalize=i == len(runs) - 1, **loop, **rescaled[kind])
-            prev = kind
-        return img
 
     def _poll_status(self, block: bool = False):
         """Status of the kernels whose workgroups wait for each other (the grouped sampler tail).  Such a launch is fail-stop: when a wait

@@ -1,6 +1,7 @@
 """The cascade's reverse-diffusion loop on the device (minimagen/Imagen.py:261-420): what a stage keeps between calls (StageState, on its
 workspace), the launcher of one step's tail kernels, and the captured HIP graphs that replay [U-Net -> tail -> step advance].
-``Imagen._stage_state`` / ``_stage_begin`` / ``_p_sample_loop`` delegate here and pass the knobs of Imagen.py (read there at call time)."""
+What a stage of a call asks for arrives as ONE ``sample_call.StageCall`` (its defaults: the reference's loop); ``Imagen._stage_state`` /
+``_stage_begin`` / ``_p_sample_loop`` delegate here and pass the knobs of Imagen.py (read there at call time)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -10,6 +11,8 @@ import torch
 
 from . import _lib as L
 from .helpers import cubic_taps, quantile_rank
+from .sample_call import Noise, StageCall, graph_key, guidance_plan, guidance_scale_table, init_start_step  # noqa: F401  (host helpers, reachable as before)
+
 
 def _drain(dev):
     if L.backend() == "hip-gfx950" and torch.cuda.is_available():
@@ -47,90 +50,16 @@ def cubic_resize(ws, img, image_size: int, stream):
     return up
 
 
-def init_start_step(steps: int, strength: float) -> int:
-    """a0, the number of steps a loop of S = ``steps`` steps skips when it starts from an init image at ``strength`` in (0, 1]: it executes its
-    last m = min(S, max(1, floor(strength S + 0.5))) steps, a0 = S - m (strength 1: the whole loop).  Host only; raises ValueError."""
-    S = int(steps)
-    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0. < float(strength) <= 1.:
-        raise ValueError(f"init_strength must be a number in (0, 1], got {strength!r}")
-    if S < 1:
-        raise ValueError(f"steps must be positive, got {steps!r}")
-    return S - min(S, max(1, int(float(strength) * S + 0.5)))
-
-
-def guidance_scale_table(tau, T: int, B: int, cond_scale: float = 1., interval=None, schedule=None) -> torch.Tensor:
-    """A stage's guidance scales in EXECUTION order (entry 0: the first step executed, the noisiest one), float64 [S] or [S, B] (per row; the
-    caller's values as they are: a run at ONE scale is the call at that cond_scale, a table run rounds them to fp32).
-    ``tau`` int64 [S]: the trained timestep of step index k (GaussianDiffusion.sampling_timestep_map; arange(T) for the reference's loop) --
-    entry i is the step at tau[S - 1 - i].  ``schedule``: None (``cond_scale`` on every step), a callable f(u) -> float with
-    u = tau_k / (T - 1), or a tensor / sequence [S] or [S, B] already in execution order.  ``interval`` = (lo, hi): a step outside
-    lo (T - 1) <= tau_k <= hi (T - 1) (float64 against the integer tau_k) gets scale 1.  Host only; raises ValueError on bad values."""
-    taus = [int(v) for v in reversed(tau.tolist())]
-    S = len(taus)
-    if schedule is None:
-        w = torch.full((S,), float(cond_scale), dtype=torch.float64)
-    elif callable(schedule):
-        vals = []
-        for t in taus:
-            v = schedule(t / (T - 1))
-            if isinstance(v, bool) or not isinstance(v, (int, float)):
-                raise ValueError(f"guidance_schedule: the callable must return a float, got {v!r}")
-            vals.append(float(v))
-        w = torch.tensor(vals, dtype=torch.float64)
-    else:
-        try:
-            w = torch.as_tensor(schedule).detach().to('cpu')
-        except Exception as e:
-            raise ValueError(f"guidance_schedule: not a tensor or a sequence of numbers ({e})")
-        if w.dtype == torch.bool or not (w.is_floating_point() or w.dtype in (torch.int32, torch.int64)):
-            raise ValueError(f"guidance_schedule: a float tensor or sequence, got dtype {w.dtype}")
-        w = w.to(torch.float64)
-        if w.dim() not in (1, 2) or w.shape[0] != S or (w.dim() == 2 and w.shape[1] != B):
-            raise ValueError(f"guidance_schedule: shape {tuple(w.shape)} is neither [{S}] (one scale per step executed) nor [{S}, {B}] (per row)")
-    if not bool(torch.isfinite(w).all()):
-        raise ValueError("guidance_schedule: the scales must be finite")
-    if interval is not None:
-        lo, hi = interval
-        inside = torch.tensor([lo * (T - 1) <= t <= hi * (T - 1) for t in taus])
-        w = torch.where(inside if w.dim() == 1 else inside[:, None], w, torch.ones_like(w))
-    return w.contiguous()
-
-
-def guidance_plan(w: torch.Tensor):
-    """The runs of a stage whose guidance scales are ``w`` (float [S] or [S, B], execution order): a list of (kind, first step, one past the
-    last step, scale), maximal runs of steps of one kind --
-      'plain'   every row's scale is exactly 1: the B-row workspace, one U-Net row per image
-      'scalar'  ONE row-uniform scale s != 1 (all the stage's guided steps share it): the existing guided path at cond_scale = s, folded where
-                it folds today; ``scale`` = s
-      'table'   anything else: the unfolded 2B-row workspace, the scale read per step and row from device memory (``scale`` = None)
-    A single 'plain' or 'scalar' run over all S steps IS the existing call at cond_scale = 1 / s: same workspaces, states, graph keys, bits."""
-    w2 = w.reshape(w.shape[0], -1).to(torch.float64)
-    S = w2.shape[0]
-    guided = [bool((w2[i] != 1.).any()) for i in range(S)]
-    values = {float(v) for i in range(S) if guided[i] for v in w2[i].tolist()}
-    one = len(values) == 1                       # (a guided step with a row at 1 beside another value has two values: a table)
-    kind = lambda i: 'plain' if not guided[i] else ('scalar' if one else 'table')
-    runs, i = [], 0
-    while i < S:
-        j = i
-        while j < S and kind(j) == kind(i):
-            j += 1
-        runs.append((kind(i), i, j, 1. if kind(i) == 'plain' else (next(iter(values)) if one else None)))
-        i = j
-    return runs
-
-
 class StageState:
-    """One stage's loop state, kept on its workspace (so it dies with the buffers it points into) per schedule -- or per (schedule, S,
-    sampler, eta) for a call with ``solver`` = (S, sampler, eta).  Every field is a slot; ``ext`` and ``group_sync`` stay UNSET until they exist
-    (``hasattr`` is how callers ask for a solver extension / a grouped tail); ``t_map`` / ``group_err_host``, None until then, answer the same here.
-    ``hw`` (pixels per channel plane) makes it the state of an INPAINTING call -- an entry of its own: the coefficient table with columns 6 and
-    7, and the known-image / mask buffers every call copies into (so one captured graph serves every later call's images and masks);
-    ``ip`` (None otherwise) is the kernels' block over them, rebuilt by every stage_begin.  ``objective`` (what the stage's U-Net predicts: 'noise',
-    'x_start' or 'v') only chooses columns 0 and 1 of the coefficient table: no kernel, struct or launch knows about it.
-    ``rescale_partials`` (None until a call with guidance_rescale > 0 runs on this state): the [B][chunks][4] fp64 sums of mi_cfg_rescale_*.
-    ``scale_tab`` (None until a 'table' run of a guidance schedule runs on this state): fp32 [S][B], row k the scales of step
-    index k, which every such call copies into -- the captured graphs address it, so they serve every later call's values."""
+    """One stage's loop state, kept on its workspace (so it dies with the buffers it points into) per schedule -- or per (schedule, S, sampler, eta) for a call with
+    ``solver`` = (S, sampler, eta).  Every field is a slot; ``ext`` and ``group_sync`` stay UNSET until they exist (``hasattr`` is how callers ask for a solver
+    extension / a grouped tail); ``t_map`` / ``group_err_host``, None until then, answer the same here. ``hw`` (pixels per channel plane) makes it the state of an
+    INPAINTING call -- an entry of its own: the coefficient table with columns 6 and 7, and the known-image / mask buffers every call copies into (so one captured
+    graph serves every later call's images and masks); ``ip`` (None otherwise) is the kernels' block over them, rebuilt by every stage_begin.  ``objective`` (what
+    the stage's U-Net predicts: 'noise', 'x_start' or 'v') only chooses columns 0 and 1 of the coefficient table: no kernel, struct or launch knows about it.
+    ``rescale_partials`` (None until a call with guidance_rescale > 0 runs on this state): the [B][chunks][4] fp64 sums of mi_cfg_rescale_*. ``scale_tab`` (None
+    until a 'table' run of a guidance schedule runs on this state): fp32 [S][B], row k the scales of step index k, which every such call copies
+    into -- the captured graphs address it, so they serve every later call's values."""
     __slots__ = ("coef", "tau", "t_map", "x0_prev", "ext", "t_state", "x0", "hist", "s_q", "v_q", "seed_dev", "graphs",
                  "group_sync", "group_err_host", "group_failed", "group_heal", "known", "mask", "ip", "known_noise", "rescale_partials", "scale_tab", "scale_tab_host")
 
@@ -172,22 +101,11 @@ class StageState:
         self.graphs.clear()
 
 
-def stage_state(ws, sched, B: int, n: int, solver=None, eng=None, max_states: int = 8, hw: int = None, objective: str = 'noise',
-                start: int = 0) -> StageState:
-    """The workspace's state for this schedule / solver setting, keyed by T for the default call and (T, S, sampler, eta) otherwise; an
-    inpainting call (``hw``) has its own: that key plus an 'inpaint' marker, bounded together with the solver states.  An ``objective`` other
-    than 'noise' (another coefficient table) is appended to the key in the same way; the keys of a noise-predicting U-Net are what they were.
-    ``start`` > 0 (a loop that skips its first steps: an init image) is part of the key for 'dpmpp_2m' only, whose table depends on it."""
+def stage_state(ws, sched, shape, call: StageCall, eng=None, max_states: int = 8) -> StageState:
+    """The workspace's state for this call's stage: keyed by ``call.state_key`` -- T for the default call; every other key is a tuple, and those
+    states (solver settings, inpainting, objectives) are bounded together.  ``shape`` = (B, C, H, W)."""
     store = ws.sampler_state
-    key = sched.num_timesteps if solver is None else (sched.num_timesteps,) + tuple(solver)
-    if not (start and solver is not None and solver[1] == 'dpmpp_2m'):
-        start = 0
-    if start:
-        key = key + (("start", start),)
-    if objective != 'noise':
-        key = (key if isinstance(key, tuple) else (key,)) + (objective,)
-    if hw is not None:
-        key = (key if isinstance(key, tuple) else (key,)) + ("inpaint",)
+    key = call.state_key(sched.num_timesteps)
     bounded = isinstance(key, tuple)
     st = store.get(key)
     if st is not None and bounded:
@@ -201,16 +119,17 @@ def stage_state(ws, sched, B: int, n: int, solver=None, eng=None, max_states: in
             if eng is not None:
                 eng.drop_step_tables(ws, old.t_state)
     if st is None:
-        st = store[key] = StageState(sched, B, n, ws.dev, solver, hw, objective, start)
+        st = store[key] = StageState(sched, shape[0], shape[1] * shape[2] * shape[3], ws.dev, call.solver, None if call.inpaint is None else shape[2] * shape[3],
+                                     call.objective, call.start)
     return st
 
 
 def known_begin(st: StageState, ws, shape, inpaint, *, sched, known_noise, seed: int, sample0: int, stage: int, stream, start: int = 0, steps: int = None):
-    """The known region of an inpainting call at this stage: the caller's images resized to the stage's size (cubic taps), clamped to [0, 1]
-    and normalised INTO st.known, the masks resized (nearest) into st.mask, and blend 0 on the x_T just drawn: the known pixels at the noise
-    level of x_T.  ``inpaint`` = (images float32 [B, C, H, W], masks uint8 [B, Hm, Wm], normalize), on the device.
-    ``start`` = a0 > 0 (the loop of ``steps`` steps begins at step a0 on an init-noised x): blend 0 at THAT level, with the known-region draw
-    a0 -- the one the tail of step a0 - 1 would have used -- through a copy of the block whose stream and buffer are moved on by a0."""
+    """The known region of an inpainting call at this stage: the caller's images resized to the stage's size (cubic taps), clamped to [0, 1] and normalised INTO
+    st.known, the masks resized (nearest) into st.mask, and blend 0 on the x_T just drawn: the known pixels at the noise level of x_T.  ``inpaint`` = (images float32
+    [B, C, H, W], masks uint8 [B, Hm, Wm], normalize), on the device. ``start`` = a0 > 0 (the loop of ``steps`` steps begins at step a0 on an init-noised x): blend 0
+    at THAT level, with the known-region draw a0 -- the one the tail of step a0 - 1 would have used -- through a copy of the block whose stream and buffer are moved
+    on by a0."""
     lib = L.lib()
     images, masks, normalize = inpaint
     B, Cc, H, W = shape
@@ -232,23 +151,21 @@ def known_begin(st: StageState, ws, shape, inpaint, *, sched, known_noise, seed:
     L.check(lib.mi_inpaint_blend0_fwd(L.ptr(ws.x), B, n, C.byref(ip0), a, b, int(seed) & 0x7FFFFFFFFFFFFFFF, sample0, stream), "mi_inpaint_blend0_fwd")
 
 
-def stage_begin(unet, shape, *, noise_scheduler, ws, noise_fn=None, seed: int = 0, sample0: int = 0, stage: int = 0, solver=None, max_states: int = 8,
-                inpaint=None, objective: str = 'noise', start: int = 0, init=None):
-    """Everything of a stage's loop that does not depend on the PREVIOUS stage's image: x_T (Imagen.py:400), the device-resident timestep, the
-    per-step conditioning tables of all T steps -- and, for an inpainting call (``inpaint``: see known_begin), the stage's known image and mask
-    and blend 0.  sample() issues it for every stage before the first stage's loop, so that a later stage's
-    stream has it done while it waits for its low-resolution input (on-device noise only: injected noise is drawn in the reference's order,
-    then the T known-region draws).
-    ``init`` = (images float32 [B, C, H, W] on the device, normalize) with ``start`` = a0: the loop begins at step a0 on
-    x = a y' + b eps -- y' the images at the stage's size in the sampler's range, (a, b) the level of the first executed step
-    (init_start_coefs), eps the stage's OWN x_T draw (same Philox stream and keying, or the same noise_fn call), made by ONE launch
-    (mi_init_noise_fwd) in place of the x_T fill; every other draw keeps its index, the device step index becomes T - 1 - a0."""
+def stage_begin(unet, shape, ws, call: StageCall, *, noise_scheduler, noise: Noise = Noise(), max_states: int = 8):
+    """Everything of a stage's loop that does not depend on the PREVIOUS stage's image: x_T (Imagen.py:400), the device-resident timestep, the per-step conditioning
+    tables of all T steps -- and, for an inpainting call (``call.inpaint``: see known_begin), the stage's known image and mask and blend 0. ``noise``: where the
+    draws come from (sample_call.Noise).  sample() issues it for every stage before the first stage's loop, so that a later stage's stream has it done while it waits
+    for its low-resolution input (on-device noise only: injected noise is drawn in the reference's order, then the T known-region draws). ``call.init`` = (images
+    float32 [B, C, H, W] on the device, normalize) with ``call.start`` = a0: the loop begins at step a0 on x = a y' + b eps -- y' the images at
+    the stage's size in the sampler's range, (a, b) the level of the first executed step (init_start_coefs), eps the stage's OWN x_T draw (same Philox stream and
+    keying, or the same noise_fn call), made by ONE launch (mi_init_noise_fwd) in place of the x_T fill; every other draw keeps its index, the device step index
+    becomes T - 1 - a0."""
     lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
     B, n = shape[0], shape[1] * shape[2] * shape[3]
-    T = noise_scheduler.num_timesteps if solver is None else solver[0]        # steps of the loop (one draw each, for every solver)
+    (noise_fn, seed, sample0), stage, solver, inpaint, start, init = noise, call.stage, call.solver, call.inpaint, call.start, call.init
+    T = call.steps                                                           # steps of the loop (one draw each, for every solver)
     assert 0 <= start < T and (init is not None or not start), (start, T)
-    st = stage_state(ws, noise_scheduler, B, n, solver, eng, max_states, hw=None if inpaint is None else shape[2] * shape[3], objective=objective,
-                     start=start)
+    st = stage_state(ws, noise_scheduler, shape, call, eng, max_states)
     noise_dev = known_noise = None
     x_t_stream = (stage << 20) | (1 << 19) | 1
 
@@ -284,23 +201,18 @@ def stage_begin(unet, shape, *, noise_scheduler, ws, noise_fn=None, seed: int = 
     return st, noise_dev
 
 
-def stage_attach(unet, shape, *, noise_scheduler, ws, first: StageState, stage: int = 0, solver=None, max_states: int = 8, inpaint=None,
-                 objective: str = 'noise', start: int = 0) -> StageState:
-    """The state of a FURTHER workspace a stage visits in this call (a guidance plan of several runs), behind stage_begin on
-    the first one: its step tables, and for an inpainting call its known image and mask, copied from ``first`` (resized once) over the same
-    known-region noise.  No draw: x, the history and the step index arrive with the hand-over (stage_handover).  ``start``: as stage_begin's
-    (it selects the state: the table of a 'dpmpp_2m' loop that skips its first steps)."""
+def stage_attach(unet, shape, ws, call: StageCall, *, noise_scheduler, first: StageState, max_states: int = 8) -> StageState:
+    """The state of a FURTHER workspace a stage visits in this call (a guidance plan of several runs), behind stage_begin on the first one: its step
+    tables, and for an inpainting call its known image and mask, copied from ``first`` (resized once) over the same known-region noise.  No draw: x, the history and
+    the step index arrive with the hand-over (stage_handover)."""
     eng = unet.engine()
-    B, n = shape[0], shape[1] * shape[2] * shape[3]
-    T = noise_scheduler.num_timesteps if solver is None else solver[0]
-    st = stage_state(ws, noise_scheduler, B, n, solver, eng, max_states, hw=None if inpaint is None else shape[2] * shape[3], objective=objective,
-                     start=start)
-    if inpaint is not None:
+    st = stage_state(ws, noise_scheduler, shape, call, eng, max_states)
+    if call.inpaint is not None:
         st.known.copy_(first.known)
         st.mask.copy_(first.mask)
         st.known_noise = first.known_noise
-        st.ip = L.MiInpaintParams(L.ptr(st.known), L.ptr(st.mask), shape[2] * shape[3], (stage << 20) | (3 << 18), L.ptr(st.known_noise))
-    eng.prepare_step_tables(ws, T, st.t_state, L.current_stream(), t_map=st.tau)
+        st.ip = L.MiInpaintParams(L.ptr(st.known), L.ptr(st.mask), shape[2] * shape[3], (call.stage << 20) | (3 << 18), L.ptr(st.known_noise))
+    eng.prepare_step_tables(ws, call.steps, st.t_state, L.current_stream(), t_map=st.tau)
     return st
 
 
@@ -356,39 +268,53 @@ def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream):
     return dict(small=small, group=group, separate=separate)[kind], advance
 
 
-def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, noise_fn=None, seed: int = 0, sample0: int = 0,
-                  stage: int = 0, use_graph: bool = True, begun=None, solver=None, group_max: int = 8, max_states: int = 8, inpaint=None,
-                  objective: str = 'noise', rescale: float = 0., steps=None, scale_tab=None, finalize: bool = True, init=None):
-    """Imagen.py:373-420 + :329-370 + :261-326: T replays of [U-Net (both guidance halves) -> CFG combine + x0 -> dynamic-threshold quantile ->
-    posterior draw -> t -= 1].  ``solver`` = (S, sampler, eta): S steps over a subsequence of the trained timesteps; the loop, the noise index and the
-    Philox stream count STEPS: the reference's loop with T = S but for the state's step -> timestep map and history buffer (``st.ext``).
-    ``objective``: what the U-Net predicts; it selects the stage state (its coefficient table) and nothing else.
-    ``rescale`` = phi > 0 (guidance rescale; on a workspace built with fold=False): two launches between the U-Net and the tail
-    leave the rescaled guided prediction in rows [0, B) of ws.pred, and the tail runs as it does behind a folded U-Net.
-    One RUN of a guidance plan (DESIGN section 24): ``steps`` = (a, b) executes the steps a .. b - 1 of the T (counted from the first executed;
-    the state's step index is T - 1 - a on entry: stage_begin or stage_handover put it there) and, with ``finalize=False``, returns None
-    instead of the image.  ``scale_tab`` (host float [T] or [T, B] in execution order; on a workspace built with fold=False): the run reads its
-    scale per step and row from the state's ``scale_tab`` -- mi_cfg_sched_combine_fwd, or the sched forms of the two rescale launches,
-    between the U-Net and the tail.
-    ``init`` (see stage_begin): the loop starts from an init image at step a = ``steps``[0] -- it only matters when the
-    stage has not begun yet (``begun`` None: injected noise), the run itself is a run (a, T) like any other."""
+def run_plan(im, unet, shape, workspaces, call: StageCall, begun, *, max_states: int = 8, **loop):
+    """A stage whose guidance plan has several runs, or reads its scales from a table: every run on the workspace of its kind
+    (``workspaces``: kind -> workspace), x / the history / the step index handed over at the run boundaries, one noise stream (``begun``: the stage_begin of
+    the first run's workspace, issued here for injected noise) -> the image.  ``loop``: noise_scheduler, noise and use_graph, as p_sample_loop takes them."""
+    runs, first = call.runs, workspaces[call.runs[0][0]]
+    if begun is None:
+        begun = im._stage_begin(unet, shape, first, call, noise_scheduler=loop["noise_scheduler"], noise=loop["noise"])
+    st0, noise_dev = begun
+    states = {kind: st0 if ws is first else stage_attach(unet, shape, ws, call, noise_scheduler=loop["noise_scheduler"], first=st0, max_states=max_states)
+              for kind, ws in workspaces.items()}
+    img = prev = None
+    for run in runs:
+        kind, a = run[:2]
+        if prev is not None:
+            stage_handover(states[prev], workspaces[prev], states[kind], workspaces[kind], shape[0], call.steps - 1 - a)
+        img = im._p_sample_loop(unet, shape, workspaces[kind], call, run, begun=(states[kind], noise_dev), finalize=run is runs[-1], **loop)
+        prev = kind
+    return img
+
+
+def p_sample_loop(im, unet, shape, ws, call: StageCall, run=None, *, noise_scheduler, noise: Noise = Noise(), use_graph: bool = True, begun=None,
+                  finalize: bool = True, group_max: int = 8, max_states: int = 8):
+    """Imagen.py:373-420 + :329-370 + :261-326: T replays of [U-Net (both guidance halves) -> CFG combine + x0 -> dynamic-threshold quantile -> posterior draw -> t -=
+    1].  ``call.solver`` = (S, sampler, eta): S steps over a subsequence of the trained timesteps; the loop, the noise index and the Philox stream count STEPS: the
+    reference's loop with T = S but for the state's step -> timestep map and history buffer (``st.ext``). ``call.objective``: what the U-Net predicts; it selects the
+    stage state (its coefficient table) and nothing else. ONE RUN of the stage's guidance plan, ``run`` = (kind, a, b, scale), default the
+    stage's only one: the steps a .. b - 1 of the T (counted from the first executed; the state's step index is T - 1 - a on entry: stage_begin or stage_handover put
+    it there) at cond_scale = ``scale`` -- or, kind 'table' (on a workspace built with fold=False), at the scales of ``call.scales`` (host float [T] or [T, B] in
+    execution order), read per step and row from the state's ``scale_tab`` by mi_cfg_sched_combine_fwd or the sched forms of the rescale launches; ``finalize=False``
+    returns None instead of the image. ``call.rescale`` = phi > 0 on a guided run (on a workspace built with fold=False): two launches between the
+    U-Net and the tail leave the rescaled guided prediction in rows [0, B) of ws.pred, and the tail runs as it does behind a folded U-Net.  ``call.init``
+    (stage_begin) only matters when the stage has not begun yet (``begun`` None: injected noise): the run itself is a run (a0, T) like any other."""
     lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
-    B, Cc, H, W = shape
+    (B, Cc, H, W), T, stage, sample0 = shape, call.steps, call.stage, noise.sample0
     n = Cc * H * W
-    T = noise_scheduler.num_timesteps if solver is None else solver[0]
+    kind_of_run, a_step, b_step, cond_scale = call.runs[0] if run is None else run
+    sched = kind_of_run == 'table'
+    cond_scale, scale_tab = (1., call.scales) if sched else (cond_scale, None)
     two = ws.B2 != ws.B
     eng.set_guidance(ws, cond_scale)
-    rescale = float(rescale)
-    assert not rescale or (two and ws.cfg_fold is None), "guidance rescale reads both halves of the prediction"
-    sched = scale_tab is not None
-    assert not sched or (two and ws.cfg_fold is None), "a table of guidance scales reads both halves of the prediction"
+    rescale = float(call.rescale) if kind_of_run != 'plain' else 0.
+    assert not (rescale or sched) or (two and ws.cfg_fold is None), "guidance rescale / a table of guidance scales reads both halves of the prediction"
     combine = two and ws.cfg_fold is None and not rescale and not sched   # guidance folded into the U-Net's tail / rescaled / combined in place: ws.pred holds B guided rows
     if begun is None:
-        begun = stage_begin(unet, shape, noise_scheduler=noise_scheduler, ws=ws, noise_fn=noise_fn, seed=seed, sample0=sample0, stage=stage, solver=solver, max_states=max_states,
-                            inpaint=inpaint, objective=objective, **({} if init is None else dict(init=init, start=0 if steps is None else steps[0])))
+        begun = stage_begin(unet, shape, ws, call, noise_scheduler=noise_scheduler, noise=noise, max_states=max_states)
     st, noise_dev = begun
-    a_step, b_step = (0, T) if steps is None else steps
-    assert 0 <= a_step < b_step <= T, steps
+    assert 0 <= a_step < b_step <= T, run
     m_steps = b_step - a_step
     if sched:                                # every call's values go into the buffer the captured launches address (row k: step index k)
         if st.scale_tab is None:
@@ -398,7 +324,7 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
         if st.scale_tab_host is None or not torch.equal(st.scale_tab_host, tab):
             st.scale_tab.copy_(tab)
             st.scale_tab_host = tab
-    k_lo, k_hi, w = quantile_rank(n, im.dynamic_thresholding_percentile)
+    rank = k_lo, k_hi, w = quantile_rank(n, im.dynamic_thresholding_percentile)
     # the whole tail in one launch: of one workgroup per image (n <= MI_SAMPLER_SMALL_N), or of <= group_max (0: never) cooperating workgroups -- but
     # for a stage state whose grouped launch ever failed (fail-stop: NaN images + the sticky error word, see Imagen._poll_status)
     fused = os.environ.get("MINIMAGEN_SAMPLER_FUSED", "1") != "0"
@@ -408,13 +334,12 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
     if st.group_heal:
         st.group_sync.zero_()               # stream-ordered behind every launch queued on this lane: ticket, counters, histograms, error word
         st.group_heal = False
-    seed = int(seed) & 0x7FFFFFFFFFFFFFFF
+    seed = int(noise.seed) & 0x7FFFFFFFFFFFFFFF
     if noise_dev is None:
         if st.seed_dev is None:
             st.seed_dev = torch.zeros(1, dtype=torch.int64, device=ws.dev)
         st.seed_dev.fill_(seed)
-    # the captured graph of `per` steps is cached per (workspace, guidance, threshold, noise mode, shard offset, tail kind); the seed is in device memory
-    gkey = (float(cond_scale), two, k_lo, k_hi, w, sample0, stage, T, noise_dev is None, group) + (() if solver is None else (tuple(solver),)) + (() if st.ip is None else ("inpaint",)) + ((("rescale", rescale),) if rescale else ()) + (("sched",) if sched else ())
+    # the captured graph of `per` steps is cached per sample_call.graph_key (the seed is in device memory);
     # `per` steps per captured graph (one replay boundary, ~9 us of idle GPU, per graph): step k addresses *t_state - k, one advance per graph
     cap = int(os.environ.get("MINIMAGEN_STEPS_PER_GRAPH", "5"))
     if m_steps == T:
@@ -423,7 +348,8 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
     else:                                    # a run of a plan: m // per graphs of per steps and one of m % per; such a graph's key carries its length
         per = max(1, min(cap, 5, m_steps))
         lengths = [per] * (m_steps // per) + ([m_steps % per] if m_steps % per else [])
-    keys = {length: gkey if m_steps == T else gkey + (("len", length),) for length in (lengths if use_graph else lengths[:1])}
+    keys = {length: graph_key(call, cond_scale, two, rank, sample0, noise_dev is None, group, st.ip is not None, rescale, sched, None if m_steps == T else length)
+            for length in (lengths if use_graph else lengths[:1])}
     if use_graph and noise_dev is None:
         # bounded: one exec per (guidance, threshold, shard offset) combination and length; the oldest go, never one this run replays
         missing = sum(1 for k in keys.values() if k not in st.graphs)
@@ -432,9 +358,8 @@ def p_sample_loop(im, unet, shape, *, noise_scheduler, ws, cond_scale: float, no
             destroy_graph(st.graphs.pop(victims.pop(0)), ws.dev)
     entries = {}
     for length, key in keys.items():
-        entries[length] = _loop_entry(im, unet, st, ws, key, length, B=B, n=n, T=T, two=two,
-                                      combine=combine, cond_scale=cond_scale, rescale=rescale, sched=sched, kind=kind, group=group, k_lo=k_lo,
-                                      k_hi=k_hi, w=w, noise_dev=noise_dev, seed=seed, sample0=sample0, stage=stage, use_graph=use_graph)
+        entries[length] = _loop_entry(im, unet, st, ws, key, length, B=B, n=n, T=T, two=two, combine=combine, cond_scale=cond_scale, rescale=rescale, sched=sched,
+                                      kind=kind, group=group, k_lo=k_lo, k_hi=k_hi, w=w, noise_dev=noise_dev, seed=seed, sample0=sample0, stage=stage, use_graph=use_graph)
     if use_graph:
         try:
             for length in lengths:

@@ -3,6 +3,7 @@
 the one new launch mi_init_noise_fwd bit for bit against numpy, the loop against a restated loop on injected noise (the project's gate,
 SURVEY.md 8(c): max|d| < 1e-4 and mean|d| < 1e-5 on [0, 1] images) and the invariants of the loop (graphs, sharding, the untouched
 default call, stages, inpainting, guidance plans)."""
+import dataclasses
 import functools
 import math
 
@@ -416,10 +417,11 @@ def test_full_strength_at_T20_is_the_plain_call(backend):
     ws = next(iter(im.unets[0].engine()._ws.values()))
     assert list(ws.sampler_state.keys()) == [20, (20, 7, "ddim", 0.)] and all(len(v.graphs) == 1 for v in ws.sampler_state.values())
     for solver in (None, (7, "ddim", 0.)):
-        begin = dict(noise_scheduler=im.noise_schedulers[0], ws=ws, seed=11, sample0=0, stage=0, solver=solver)
-        S.stage_begin(im.unets[0], (2, 3, 16, 16), **begin)
+        begin = dict(noise_scheduler=im.noise_schedulers[0], noise=S.Noise(seed=11, sample0=0))
+        plain = S.StageCall(0, 20 if solver is None else solver[0], solver)
+        S.stage_begin(im.unets[0], (2, 3, 16, 16), ws, plain, **begin)
         x_t = ws.x.clone()
-        S.stage_begin(im.unets[0], (2, 3, 16, 16), **begin, start=0, init=(y, True))
+        S.stage_begin(im.unets[0], (2, 3, 16, 16), ws, dataclasses.replace(plain, start=0, init=(y, True)), **begin)
         assert torch.equal(ws.x, x_t) and x_t.isfinite().all() and x_t.std() > 0.5, solver
     im.check_device_status()
 

@@ -544,8 +544,8 @@ def test_skipped_stages_launch_nothing(backend, monkeypatch):
     emb, mask = R.synthetic_text(1, length=8, seed=1)
     ran, begun = [], []
     loop, begin = im._p_sample_loop, im._stage_begin
-    monkeypatch.setattr(im, "_p_sample_loop", lambda unet, shape, **kw: (ran.append(kw["stage"]), loop(unet, shape, **kw))[1])
-    monkeypatch.setattr(im, "_stage_begin", lambda unet, shape, **kw: (begun.append(kw["stage"]), begin(unet, shape, **kw))[1])
+    monkeypatch.setattr(im, "_p_sample_loop", lambda unet, shape, ws, call, *a, **kw: (ran.append(call.stage), loop(unet, shape, ws, call, *a, **kw))[1])
+    monkeypatch.setattr(im, "_stage_begin", lambda unet, shape, ws, call, **kw: (begun.append(call.stage), begin(unet, shape, ws, call, **kw))[1])
     kw = dict(text_embeds=emb, text_masks=mask, cond_scale=2., _seed=3, sample_steps=2)
     a = im.sample(**kw, stop_at_stage=1)
     assert a.shape == (1, 3, 8, 8) and ran == [0] and begun == [0]

@@ -6,6 +6,7 @@ import torch
 from minimagen_amd import _lib as L
 from minimagen_amd.Imagen import Imagen
 from minimagen_amd.Unet import Unet
+from minimagen_amd.sample_call import StageCall
 from oracle import restated as R
 from tests import _inputs as I
 from tests._backend import BACKENDS, GPU_ONLY, setup
@@ -78,7 +79,7 @@ def test_step_golden(backend):
         ws = eng.workspace(B, 2 * B, 64, 64)
         stream = L.current_stream()
         eng.set_text(ws, emb.to(dev), mask.to(dev), torch.cat((torch.ones(B, dtype=torch.bool), torch.zeros(B, dtype=torch.bool))))
-        sstate = im._stage_state(ws, sched, B, n)
+        sstate = im._stage_state(ws, sched, (B, 3, 64, 64), StageCall(0, T))
         ws.x.copy_(x)
         noise_dev = torch.zeros(T, B, 3, 64, 64, device=dev)
         noise_dev[T - 1 - t] = noise.to(dev)                       # mi_posterior_fwd reads the draw of step index T-1-t
@@ -550,6 +551,17 @@ def test_sample_notices_weight_updates_made_through_data(backend):
     im2 = im2.to(dev)
     assert torch.equal(im2.sample(**args), b)
     assert torch.equal(im.sample(**args), b)                 # and the steady state stays on the new packs
+    # the call that is issued again keeps its keywords: the same kind of update, followed by a call with non-default ones
+    g = torch.Generator().manual_seed(6)
+    more = dict(args, sample_steps=5, sampler="ddim", init_images=torch.rand(2, 3, S, S, generator=g).to(dev), init_strength=0.6)
+    with torch.no_grad():
+        for name, prm in im.unets[0].named_parameters():
+            if name.endswith("final_conv.weight") or "init_conv" in name:
+                prm.data.mul_(0.8)
+    c = im.sample(**more).clone()
+    im3 = Imagen([Unet(**kw)], text_encoder_name="t5_small", image_sizes=[S], timesteps=25, cond_drop_prob=0.15)
+    im3.unets[0].load_state_dict({k: v.detach().cpu() for k, v in im.unets[0].state_dict().items()})
+    assert torch.equal(im3.to(dev).sample(**more), c) and not torch.equal(im2.sample(**more), c)
 
 
 @pytest.mark.parametrize("backend", BACKENDS)
