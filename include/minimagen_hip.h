@@ -488,6 +488,21 @@ int mi_sampler_step_small_inpaint_fwd(const mi_cfg_x0_params* c, const mi_quanti
                                       const mi_inpaint_params* ip, void* stream);
 int mi_sampler_step_group_inpaint_fwd(const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp, const mi_sampler_ext_params* e,
                                       const mi_inpaint_params* ip, void* sync, void* stream);
+/* The tail of a step whose x0 is NOT bounded by the dynamic threshold (Imagen.sample(thresholding='static' / 'none'), not in the
+ * reference): without the quantile nothing of an image meets, so the whole tail is ONE elementwise launch over a grid of (chunks, B) at every
+ * image size -- no LDS, no atomics, no sync buffer, no x0 / histogram buffers.  Per element, every operation rounded on its own, in the order
+ * of the other tails (row = coef + 8 * step):
+ *   pred = two ? null + (cond - null) * cond_scale : cond ; x0 = row[0]*x_t - row[1]*pred
+ *   clip == 1 (static):  x0 = clamp(x0, -1, 1)   (NaN stays NaN, as torch.clamp; the bits of the dynamic tails at a threshold scale of 1)
+ *   clip == 0 (none):    x0 as predicted
+ *   mean = row[2]*x0 + row[3]*x_t ; mean = mean + row[5]*x0_prev ; x = mean + row[4]*z ; x0_prev = x0 ; then the masked replace of ip
+ * with the history term only when e carries x0_prev, z as in mi_posterior_fwd (pp->noise or Philox) and the known region as in the
+ * *_inpaint_fwd tails.  e and ip may be NULL.  The blocks describe one step as for the fused tails: c->B == pp->B, c->n == pp->n,
+ * c->x_t == pp->x, one coef table and one t_state / t_off, else MI_ERR_INVALID; ip as in the *_inpaint_fwd tails; any other clip:
+ * MI_ERR_INVALID.  c->x0, c->pred_out, c->hist0, pp->x0 and pp->s_q are not used.  16-byte accesses when n % 4 == 0, element by element
+ * otherwise.  Added within ABI 12 (no struct, no existing entry changed). */
+int mi_sampler_step_direct_fwd(const mi_cfg_x0_params* c, const mi_posterior_params* pp, const mi_sampler_ext_params* e, const mi_inpaint_params* ip, int clip,
+                               void* stream);
 /* blend 0: x[b][i] = mask ? a*y + b*z'_0 : x[b][i], same operation order, z'_0 = ip->known_noise[0][b][i] or Philox stream ip->known_stream */
 int mi_inpaint_blend0_fwd(float* x, int B, int n, const mi_inpaint_params* ip, float a, float b, uint64_t seed, int sample0, void* stream);
 /* a stage's known image and mask from the caller's, already at the stage's size (img [B][n]): known = clamp(img, 0, 1), then *2-1 when

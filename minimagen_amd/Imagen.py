@@ -213,6 +213,7 @@ class Imagen(nn.Module):
 
     _parse_solver, _parse_inpaint, _parse_init = sample_call.parse_solver, sample_call.parse_inpaint, sample_call.parse_init         # (host: sample_call.py)
     _parse_guidance, _parse_guidance_schedule = sample_call.parse_guidance, sample_call.parse_guidance_schedule
+    _parse_thresholding = sample_call.parse_thresholding
 
     def _lowres_conditioning(self, unet: Unet, img, image_size: int, ws, lowres_noise_level: float, noise_fn, seed, sample0, stage):
         """Imagen.py:479-485 + :393: cubic resize (reflect pad) -> q_sample at int(T*level) -> *2-1."""
@@ -245,7 +246,7 @@ class Imagen(nn.Module):
                start_at_stage: int = None, stop_at_stage: int = None,
                negative_texts: Union[str, List[str]] = None, negative_text_embeds: torch.Tensor = None, negative_text_masks: torch.Tensor = None,
                guidance_rescale: float = None, guidance_interval=None, guidance_schedule=None,
-               init_images: torch.Tensor = None, init_strength=None):
+               init_images: torch.Tensor = None, init_strength=None, thresholding='dynamic', thresholding_percentile=None):
         """minimagen/Imagen.py:424-510.  Private keyword-only extras (not in the reference): ``_noise(shape)`` injects a
         host noise stream in the reference's draw order (parity runs); otherwise noise is Philox keyed by
         (``_seed``, ``_sample_offset`` + row, stage, step, element) so a sharded batch reproduces the unsharded one;
@@ -305,6 +306,17 @@ class Imagen(nn.Module):
         step of the FULL loop ([S] / [S, B] keep their shape, entry a0 is the first one executed; "one guided step somewhere" means an
         executed one).  One strength per stage, not per row; no RePaint resampling.  Nothing here has been tried on a trained model:
         what is checked is the arithmetic.
+
+        How x0 is bounded (keyword-only, not in the reference).  ``thresholding`` = 'dynamic' (default: the reference's
+        x0 = clamp(x0, -s, s) / s with s = max(1, the per-image quantile of |x0|)), 'static' (x0 = clamp(x0, -1, 1), the baseline of the Imagen
+        paper; a NaN stays NaN) or 'none' (x0 as predicted: what exact DDIM needs) -- one value for every stage, or a list / tuple with one per
+        stage (None there: 'dynamic').  ``thresholding_percentile`` = a number in [0, 1] for every stage, or a list with a number or None per
+        stage, stands in for ``dynamic_thresholding_percentile`` for this call; only for stages whose mode is 'dynamic' (ValueError for a stage
+        that runs with 'static' or 'none').  Everything behind x0 -- the posterior or solver step, the 'dpmpp_2m' history, the draw, the
+        inpainting blend, the final clamp to [-1, 1] of the image -- sees the x0 of the chosen mode; both go with every setting above.  A
+        'static' or 'none' stage has no quantile to select, so the tail of its step is ONE elementwise launch at every image size
+        (mi_sampler_step_direct_fwd): no cooperating workgroups, no status word.  With 'none' and a noise-predicting U-Net x0 grows without
+        bound at the noisy end and the image saturates: the mode is meant for 'v' / 'x_start' models and deterministic solvers.
 
         For every keyword family: bad values, lengths and shapes raise ValueError before anything is launched (sample_call.parse), and a
         family that is left out is a ``StageCall`` field at its default -- such a call goes through exactly the workspaces, states, tables,

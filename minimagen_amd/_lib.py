@@ -319,6 +319,8 @@ def _bind(lib):
     lib.mi_posterior_inpaint_fwd.argtypes = [vp, vp, vp, vp]
     lib.mi_sampler_step_small_inpaint_fwd.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.mi_sampler_step_group_inpaint_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.mi_sampler_step_direct_fwd.argtypes = [vp, vp, vp, vp, i32, vp]
+    lib.mi_sampler_step_direct_fwd.restype = i32
     lib.mi_inpaint_blend0_fwd.argtypes = [vp, i32, i32, vp, f32, f32, u64, i32, vp]
     lib.mi_inpaint_prepare_fwd.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, vp, i32, vp]
     lib.mi_randn_fill.argtypes = [vp, i32, i32, u64, i32, i32, vp]

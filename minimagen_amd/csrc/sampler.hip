@@ -1,5 +1,5 @@
 // Sampler epilogue kernels: K11 (CFG combine + x0), K12 (bit-exact dynamic-threshold quantile),
-// K13/K15 (posterior step, final clamp), K14 (cubic resize + low-res augmentation) and the
+// K13/K15 (posterior step, final clamp), the tail without the select (static clip / no clip), K14 (cubic resize + low-res augmentation) and the
 // counter-based normal generator.  All elementwise math keeps the reference's operation order
 // with un-fused multiplies/adds (__fmul_rn/__fadd_rn) so the only differences to the reference's
 // fp32 results come from the U-Net's summation order.
@@ -71,11 +71,16 @@ __device__ __forceinline__ float threshold_from_ranks(unsigned prefix0, unsigned
 }
 __device__ __forceinline__ float threshold_scale(float sq) { return (sq < 1.0f) ? 1.0f : sq; }      // Imagen.py:320 clamp_(min=1.): a NaN threshold stays NaN, as in torch
 
-// x_{t-1} of one element.  HISTORY: plus c5 * (the PREVIOUS step's thresholded x0, in pv), and pv becomes this step's for the next one
-template <bool HISTORY>
+// x_{t-1} of one element.  HISTORY: plus c5 * (the PREVIOUS step's thresholded x0, in pv), and pv becomes this step's for the next one.
+// CLIP: how x0 is bounded first -- CLIP_DYNAMIC clamp(x0, -s, s) / s with the image's threshold scale s (the reference; the default, and the
+// instructions this helper always had), CLIP_STATIC clamp(x0, -1, 1) (the bits of CLIP_DYNAMIC at s = 1.0f: a division by 1 is exact, so it
+// is not issued; s is not read), CLIP_NONE x0 as predicted (s is not read)
+enum { CLIP_NONE = 0, CLIP_STATIC = 1, CLIP_DYNAMIC = 2 };
+template <bool HISTORY, int CLIP = CLIP_DYNAMIC>
 __device__ __forceinline__ float posterior_elem(float x0, float x, float z, float s, const step_coef& cf, float& pv) {
     const float c1 = cf.c1, c2 = cf.c2;
-    x0 = __fdiv_rn(x0 != x0 ? x0 : fminf(fmaxf(x0, -s), s), s);               // Imagen.py:323 (torch.clamp propagates NaN)
+    if constexpr (CLIP == CLIP_DYNAMIC) x0 = __fdiv_rn(x0 != x0 ? x0 : fminf(fmaxf(x0, -s), s), s);      // Imagen.py:323 (torch.clamp propagates NaN)
+    if constexpr (CLIP == CLIP_STATIC) x0 = x0 != x0 ? x0 : fminf(fmaxf(x0, -1.0f), 1.0f);
     float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, x));                // diffusion_model.py:118-121
     if constexpr (HISTORY) { mean = __fadd_rn(mean, __fmul_rn(cf.c5, pv)); pv = x0; }
     return __fadd_rn(mean, __fmul_rn(cf.sigma, z));                            // Imagen.py:370
@@ -461,6 +466,43 @@ __global__ __launch_bounds__(SS_NT) void sampler_small_kernel(const mi_cfg_x0_pa
     }
 }
 
+// ------------------------------------------------------------------ K11 epilogue + K13 in one launch, without the radix select (any image size)
+// The tail of a step whose x0 is bounded by a constant (CLIP_STATIC) or not at all (CLIP_NONE): nothing of an image meets, so the step is
+// elementwise -- a grid of (chunks, B) workgroups of 256, every work-item its quads of one image from the prediction to the store of x_{t-1}.
+// No LDS, no atomics, no sync buffer, no x0 / histogram round trip.  Per element the operations of cfg_x0_kernel and posterior_kernel in their
+// order (guided_x0, posterior_elem<HISTORY, CLIP>, known_step4): CLIP_STATIC gives the bits of the dynamic tails wherever their scale is 1.
+template <int CLIP, bool HISTORY, bool INPAINT, typename... EXT>
+__global__ __launch_bounds__(256) void sampler_direct_kernel(const mi_cfg_x0_params c, const mi_posterior_params pp, const EXT... ext) {
+    static_assert(CLIP == CLIP_STATIC || CLIP == CLIP_NONE, "the dynamic threshold needs the select: sampler_small / sampler_group / the separate kernels");
+    static_assert(sizeof...(EXT) == (HISTORY ? 1 : 0) + (INPAINT ? 1 : 0), "the history kernels take mi_sampler_ext_params, the inpainting kernels mi_inpaint_params");
+    const int b = blockIdx.y, n = c.n, nq = (n + 3) / 4;
+    const int t = *c.t_state - c.t_off;
+    const step_coef cf = load_step_coef<HISTORY>(c.coef, t);
+    float* const prev = x0_prev_of(ext...);
+    [[maybe_unused]] const mi_inpaint_params ip = known_of(ext...);
+    const bool vec = (n & 3) == 0;
+    const size_t ob = (size_t)b * n, on = (size_t)(b + c.B) * n;
+    const int k = (pp.T - 1) - t;
+    for (int qd = blockIdx.x * 256 + threadIdx.x; qd < nq; qd += gridDim.x * 256) {
+        float cc[4], nl[4], x[4], z[4], pv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        ld_quad(c.pred2 + ob, 4 * qd, n, vec, cc);
+        if (c.two) ld_quad(c.pred2 + on, 4 * qd, n, vec, nl);
+        else { nl[0] = cc[0]; nl[1] = cc[1]; nl[2] = cc[2]; nl[3] = cc[3]; }
+        ld_quad(c.x_t + ob, 4 * qd, n, vec, x);
+        step_noise4(pp, b, k, qd, n, vec, z);
+        if constexpr (HISTORY) ld_quad(prev + ob, 4 * qd, n, vec, pv);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {                                                                    // (past the row's end: on zeros, not stored)
+            float pr;
+            const float x0 = guided_x0(cc[e], nl[e], x[e], c.two, c.cond_scale, cf, pr);
+            x[e] = posterior_elem<HISTORY, CLIP>(x0, x[e], z[e], 1.0f, cf, pv[e]);
+        }
+        if constexpr (INPAINT) known_step4(ip, pp, b, t, k, qd, n, vec, x);
+        st_quad(pp.x + ob, 4 * qd, n, vec, x);
+        if constexpr (HISTORY) st_quad(prev + ob, 4 * qd, n, vec, pv);
+    }
+}
+
 // set (set == 1) or advance (by value when set == 2, else by 1) the device-resident step and the timestep the U-Net's conditioning sees.
 // MAPPED, a step -> trained-timestep map: *t_state stays the STEP index k (what the coefficient table, the step tables and the noise
 // are indexed by), times[b] = t_map[k].  Past the last step (k < 0: the advance behind step 0) times keep t_map[0]; nothing reads them
@@ -772,13 +814,14 @@ extern "C" int mi_quantile_fwd(const mi_quantile_params* p, void* stream) {
     return mi_check_launch("quantile kernels");
 }
 
-// what the two fused tails ask of their three parameter blocks (the blocks of the separate kernels, describing ONE step)
+// what the fused tails ask of their parameter blocks (the blocks of the separate kernels, describing ONE step); q == NULL: a tail without
+// the select (mi_sampler_step_direct_fwd)
 static int check_step_params(const char* name, const mi_cfg_x0_params* c, const mi_quantile_params* q, const mi_posterior_params* pp) {
-    if (c->B <= 0 || c->n <= 0 || q->B != c->B || pp->B != c->B || q->n != c->n || pp->n != c->n) { mi_set_error("%s: inconsistent B / n", name); return MI_ERR_INVALID; }
+    if (c->B <= 0 || c->n <= 0 || pp->B != c->B || pp->n != c->n || (q && (q->B != c->B || q->n != c->n))) { mi_set_error("%s: inconsistent B / n", name); return MI_ERR_INVALID; }
     if (!c->x_t || !c->coef || !c->t_state || !pp->x || c->t_state != pp->t_state || c->t_off != pp->t_off || c->coef != pp->coef || c->x_t != pp->x) {
         mi_set_error("%s: needs x_t == x, one coef table and one t_state / t_off for the step", name); return MI_ERR_INVALID;
     }
-    if (q->k_lo < 0 || q->k_hi >= q->n || q->k_lo > q->k_hi) { mi_set_error("%s: bad ranks", name); return MI_ERR_INVALID; }
+    if (q && (q->k_lo < 0 || q->k_hi >= q->n || q->k_lo > q->k_hi)) { mi_set_error("%s: bad ranks", name); return MI_ERR_INVALID; }
     return MI_OK;
 }
 
@@ -870,6 +913,26 @@ extern "C" int mi_posterior_ext_fwd(const mi_posterior_params* p, const mi_sampl
 extern "C" int mi_posterior_inpaint_fwd(const mi_posterior_params* p, const mi_sampler_ext_params* e, const mi_inpaint_params* ip, void* stream) {
     if (!ip) return mi_posterior_ext_fwd(p, e, stream);
     return posterior_step("mi_posterior_inpaint_fwd", p, (e && e->x0_prev) ? e : nullptr, ip, stream);
+}
+
+// the tail without the select: one launch over (chunks, B); e without x0_prev (or NULL) and ip == NULL choose the plain instantiations
+template <int CLIP>
+static void sampler_step_direct(const mi_cfg_x0_params* c, const mi_posterior_params* pp, const mi_sampler_ext_params* e, const mi_inpaint_params* ip, hipStream_t st) {
+    const dim3 grid(grid_for((c->n + 3) / 4, 256), c->B), wg(256);
+    if (e && ip) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_direct_kernel<CLIP, true, true, mi_sampler_ext_params, mi_inpaint_params>), grid, wg, 0, st, *c, *pp, *e, *ip);
+    else if (ip) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_direct_kernel<CLIP, false, true, mi_inpaint_params>), grid, wg, 0, st, *c, *pp, *ip);
+    else if (e) hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_direct_kernel<CLIP, true, false, mi_sampler_ext_params>), grid, wg, 0, st, *c, *pp, *e);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(sampler_direct_kernel<CLIP, false, false>), grid, wg, 0, st, *c, *pp);
+}
+extern "C" int mi_sampler_step_direct_fwd(const mi_cfg_x0_params* c, const mi_posterior_params* pp, const mi_sampler_ext_params* e, const mi_inpaint_params* ip, int clip,
+                                          void* stream) {
+    if (clip != CLIP_STATIC && clip != CLIP_NONE) { mi_set_error("mi_sampler_step_direct_fwd: clip = %d (1: static clamp to [-1, 1], 0: none)", clip); return MI_ERR_INVALID; }
+    if (const int rc = check_step_params("mi_sampler_step_direct_fwd", c, nullptr, pp)) return rc;
+    if (const int rc = check_inpaint_params("mi_sampler_step_direct_fwd", ip, c->n)) return rc;
+    if (!(e && e->x0_prev)) e = nullptr;
+    if (clip == CLIP_STATIC) sampler_step_direct<CLIP_STATIC>(c, pp, e, ip, (hipStream_t)stream);
+    else sampler_step_direct<CLIP_NONE>(c, pp, e, ip, (hipStream_t)stream);
+    return mi_check_launch("sampler_direct_kernel");
 }
 
 // blend 0 and the per-stage preparation of an inpainting call

@@ -60,7 +60,9 @@ def sample_distributed(imagen, *, text_embeds: torch.Tensor, text_masks: Optiona
     statistics are per image, so sharding changes no bit).  ``guidance_interval`` goes through; of a ``guidance_schedule`` (one entry per
     stage) every [S, B] entry (per row, full batch) is sharded along dimension 1 by the same bounds, everything else goes through.
     ``init_images`` (full batch) is sharded with the captions' rows and ``init_strength`` goes through: the init noise is the stage's own
-    x_T draw, keyed by the global row like every other, so the gathered batch equals the unsharded call here too."""
+    x_T draw, keyed by the global row like every other, so the gathered batch equals the unsharded call here too.
+    ``thresholding`` / ``thresholding_percentile`` go through: the bound on x0 is per image (the dynamic quantile) or per element ('static',
+    'none'), so sharding changes no bit."""
     ws = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     batch = text_embeds.shape[0]

@@ -92,7 +92,8 @@ def sample_and_save(captions: list, *, minimagen: Optional[Imagen] = None, train
     ``sampler_eta`` (e.g. ``dict(cond_scale=3., sample_steps=25, sampler='dpmpp_2m')``) among them, and the pixel inputs ``inpaint_images`` /
     ``inpaint_masks`` / ``start_image`` / ``start_at_stage`` / ``stop_at_stage`` (one row per caption), and the guidance extras ``negative_texts`` (one string, or one per caption) /
     ``negative_text_embeds`` / ``negative_text_masks`` / ``guidance_rescale``, and the guidance over the steps ``guidance_interval`` / ``guidance_schedule``,
-    and the starting image ``init_images`` (one row per caption) / ``init_strength``.  ``ema=True`` loads the training
+    and the starting image ``init_images`` (one row per caption) / ``init_strength``, and how x0 is bounded,
+    ``thresholding`` ('dynamic' / 'static' / 'none') / ``thresholding_percentile``.  ``ema=True`` loads the training
     directory's averaged weights (``load_minimagen(..., ema=True)``); it needs ``training_directory``."""
     assert not (minimagen is None and training_directory is None), \
         "Must supply either a training directory or MinImagen instance."

@@ -128,6 +128,8 @@ class StageCall:
     runs: tuple = ()                             # the guidance plan, (kind, first step, one past the last, scale) (guidance_plan)
     scales: Optional[torch.Tensor] = None        # the stage's guidance scales, [S] or [S, B] in execution order, for its 'table' runs
     rescale: float = 0.                          # phi of guidance rescale, applied on the guided runs
+    threshold: str = 'dynamic'                   # how x0 is bounded: 'dynamic' (the reference), 'static' (clamp to [-1, 1]) or 'none'
+    percentile: Optional[float] = None           # the dynamic threshold's percentile for this call (None: the model's)
 
     @property
     def kinds(self):                             # the workspaces the stage visits, first run's first
@@ -145,10 +147,11 @@ class StageCall:
 def graph_key(call: StageCall, cond_scale: float, two: bool, rank, sample0: int, device_noise: bool, group: bool, known: bool,
               rescale: float, sched: bool, length: int = None):
     """The key of a captured graph on its StageState: guidance, threshold rank (k_lo, k_hi, w), shard offset, stage, loop length, noise mode, tail
-    kind, then -- each only when it is on -- the solver, "inpaint", ("rescale", phi), "sched", and ("len", steps) for a run shorter than the loop."""
+    kind, then -- each only when it is on -- the solver, "inpaint", ("rescale", phi), "sched", ("len", steps) for a run shorter than the loop, and
+    ("thr", mode) for a stage whose x0 is not bounded by the dynamic threshold (a percentile of the call's is in the rank already)."""
     return (float(cond_scale), two, *rank, sample0, call.stage, call.steps, device_noise, group) + (() if call.solver is None else (tuple(call.solver),)) \
         + (("inpaint",) if known else ()) + ((("rescale", rescale),) if rescale else ()) + (("sched",) if sched else ()) \
-        + (() if length is None else (("len", length),))
+        + (() if length is None else (("len", length),)) + (() if call.threshold == 'dynamic' else (("thr", call.threshold),))
 
 
 @dataclasses.dataclass(frozen=True)
@@ -329,10 +332,32 @@ def parse_guidance_schedule(model, batch_size: int, cond_scale, solvers, guidanc
     return tables
 
 
+THRESHOLDING = ('dynamic', 'static', 'none')
+
+
+def parse_thresholding(model, thresholding, thresholding_percentile, first_stage: int, end_stage: int):
+    """-> per stage (mode, percentile or None: the model's).  ``thresholding``: one of THRESHOLDING for every stage, or a list / tuple with one per
+    stage (None there: 'dynamic'); ``thresholding_percentile``: None, a number in [0, 1] for every stage, or a list / tuple with a number or None
+    per stage -- for 'dynamic' stages only.  Every entry's value is validated; a percentile on a 'static' / 'none' stage the call does not run is
+    ignored.  Host only; raises ValueError on bad values."""
+    n_stages = len(model.unets)
+    modes = ['dynamic' if m is None else m for m in per_stage(thresholding, n_stages, "thresholding")]
+    for m in modes:
+        reject(not isinstance(m, str) or m not in THRESHOLDING, f"thresholding must be one of {THRESHOLDING} (or None in a list: 'dynamic'), got {m!r}")
+    pcts = per_stage(thresholding_percentile, n_stages, "thresholding_percentile", noun="entry")
+    for p in pcts:
+        reject(p is not None and (not is_number(p) or not 0. <= float(p) <= 1.),
+               f"thresholding_percentile must be a number in [0, 1] (or None), got {p!r}")
+    for stage in range(first_stage, end_stage):
+        reject(pcts[stage] is not None and modes[stage] != 'dynamic',
+               f"thresholding_percentile goes with thresholding='dynamic' only: stage {stage} is {modes[stage]!r}")
+    return [(m, None if p is None else float(p)) for m, p in zip(modes, pcts)]
+
+
 def parse(model, *, texts, text_masks, text_embeds, cond_scale, lowres_sample_noise_level, return_pil_images, device, _noise, _seed,
           _sample_offset, _use_graph, _precision, _async, sample_steps, sampler, sampler_eta, inpaint_images, inpaint_masks, start_image,
           start_at_stage, stop_at_stage, negative_texts, negative_text_embeds, negative_text_masks, guidance_rescale, guidance_interval,
-          guidance_schedule, init_images, init_strength) -> SampleCall:
+          guidance_schedule, init_images, init_strength, thresholding, thresholding_percentile) -> SampleCall:
     """Every keyword of ``Imagen.sample()`` (all of them, by name: one that is not listed here is a TypeError, never silently dropped) -> the SampleCall.  Host work
     only, so every ValueError -- and the assertions on the captions and on guidance without conditional dropout -- is raised before anything is launched."""
     solvers = parse_solver(model, sample_steps, sampler, sampler_eta)
@@ -340,6 +365,7 @@ def parse(model, *, texts, text_masks, text_embeds, cond_scale, lowres_sample_no
     n_rows = text_embeds.shape[0] if text_embeds is not None else len(texts)
     first_stage, end_stage, inpaint, start_image = parse_inpaint(model, n_rows, inpaint_images, inpaint_masks, start_image, start_at_stage, stop_at_stage)
     init_images, init_starts = parse_init(model, n_rows, init_images, init_strength, solvers, first_stage, end_stage)
+    thresholds = parse_thresholding(model, thresholding, thresholding_percentile, first_stage, end_stage)
     scale_tabs = parse_guidance_schedule(model, n_rows, cond_scale, solvers, guidance_interval, guidance_schedule)
     guided = None
     if scale_tabs is not None:                               # (of the steps a stage executes: a loop that starts at an init image skips its first ones)
@@ -361,7 +387,7 @@ def parse(model, *, texts, text_masks, text_embeds, cond_scale, lowres_sample_no
         runs = [('plain' if cond_scale == 1. else 'scalar', a0, n_steps, cond_scale)] if w_stage is None else \
             [(kind, a + a0, b + a0, scale) for kind, a, b, scale in guidance_plan(w_stage[a0:])]
         stages.append(StageCall(stage, n_steps, solvers[stage], a0, model.pred_objectives[stage], inpaint,
-                                None if init_starts[stage] is None else (init_images, normalize), tuple(runs), w_stage, rescale))
+                                None if init_starts[stage] is None else (init_images, normalize), tuple(runs), w_stage, rescale, *thresholds[stage]))
     assert model.can_classifier_guidance or all(kind == 'plain' for s in stages for kind, *_ in s.runs), \
         'imagen was not trained with conditional dropout, and thus one cannot use classifier free guidance (cond_scale anything other than 1)'
     return SampleCall(

@@ -229,9 +229,10 @@ def stage_handover(src: StageState, ws_src, dst: StageState, ws_dst, B: int, ste
         L.check(lib.mi_step_set_mapped(L.ptr(dst.t_state), L.ptr(ws_dst.times), B, step, C.byref(dst.ext), stream), "mi_step_set_mapped")
 
 
-def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream):
+def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream, clip: int = None):
     """What follows the U-Net evaluation in a step, fixed once per graph entry -> (launch, advance): ``launch(k)`` enqueues the tail kernels of
-    step *t_state - k (``kind``: "small" one workgroup per image | "group" cooperating workgroups | "separate" kernels), ``advance(n)`` moves the
+    step *t_state - k (``kind``: "small" one workgroup per image | "group" cooperating workgroups | "separate" kernels | "direct" the one elementwise launch
+    of a stage without the dynamic threshold, ``clip`` = 1 static clamp / 0 none: mi_sampler_step_direct_fwd, at every image size), ``advance(n)`` moves the
     device-resident step by n (mapped entries when the state has a step -> timestep map).  Always the *_ext_fwd tails: without st.ext / a history buffer they ARE the plain ones;
     the *_inpaint_fwd tails for the state of an inpainting call (chosen here, once: a step has no branch for it)."""
     lib, tails = L.lib(), {}
@@ -261,11 +262,15 @@ def tail_launcher(st: StageState, ws, kind: str, cp, qp, pp, stream):
         L.check(lib.mi_quantile_fwd(q_, stream), "mi_quantile_fwd")
         L.check(posterior_fwd(p_, *blocks, stream), f"mi_posterior_{form}_fwd")
 
+    def direct(k=0):
+        c_, _, p_ = params(k)
+        L.check(lib.mi_sampler_step_direct_fwd(c_, p_, ext, None if st.ip is None else C.byref(st.ip), clip, stream), "mi_sampler_step_direct_fwd")
+
     if st.t_map is None:
         advance = lambda n=1: L.check(lib.mi_step_advance_by(*state, n, stream), "mi_step_advance_by")
     else:
         advance = lambda n=1: L.check(lib.mi_step_advance_by_mapped(*state, n, ext, stream), "mi_step_advance_by_mapped")
-    return dict(small=small, group=group, separate=separate)[kind], advance
+    return dict(small=small, group=group, separate=separate, direct=direct)[kind], advance
 
 
 def run_plan(im, unet, shape, workspaces, call: StageCall, begun, *, max_states: int = 8, **loop):
@@ -290,7 +295,7 @@ def run_plan(im, unet, shape, workspaces, call: StageCall, begun, *, max_states:
 
 def p_sample_loop(im, unet, shape, ws, call: StageCall, run=None, *, noise_scheduler, noise: Noise = Noise(), use_graph: bool = True, begun=None,
                   finalize: bool = True, group_max: int = 8, max_states: int = 8):
-    """Imagen.py:373-420 + :329-370 + :261-326: T replays of [U-Net (both guidance halves) -> CFG combine + x0 -> dynamic-threshold quantile -> posterior draw -> t -=
+    """Imagen.py:373-420 + :329-370 + :261-326: T replays of [U-Net (both guidance halves) -> CFG combine + x0 -> dynamic-threshold quantile (``call.threshold`` 'dynamic'; 'static' / 'none': no select, the one-launch direct tail) -> posterior draw -> t -=
     1].  ``call.solver`` = (S, sampler, eta): S steps over a subsequence of the trained timesteps; the loop, the noise index and the Philox stream count STEPS: the
     reference's loop with T = S but for the state's step -> timestep map and history buffer (``st.ext``). ``call.objective``: what the U-Net predicts; it selects the
     stage state (its coefficient table) and nothing else. ONE RUN of the stage's guidance plan, ``run`` = (kind, a, b, scale), default the
@@ -324,12 +329,14 @@ def p_sample_loop(im, unet, shape, ws, call: StageCall, run=None, *, noise_sched
         if st.scale_tab_host is None or not torch.equal(st.scale_tab_host, tab):
             st.scale_tab.copy_(tab)
             st.scale_tab_host = tab
-    rank = k_lo, k_hi, w = quantile_rank(n, im.dynamic_thresholding_percentile)
+    rank = k_lo, k_hi, w = quantile_rank(n, im.dynamic_thresholding_percentile if call.percentile is None else call.percentile)
     # the whole tail in one launch: of one workgroup per image (n <= MI_SAMPLER_SMALL_N), or of <= group_max (0: never) cooperating workgroups -- but
-    # for a stage state whose grouped launch ever failed (fail-stop: NaN images + the sticky error word, see Imagen._poll_status)
+    # for a stage state whose grouped launch ever failed (fail-stop: NaN images + the sticky error word, see Imagen._poll_status).  A stage without the
+    # dynamic threshold has nothing to select: "direct", ONE elementwise launch at every size, whatever the knobs say
     fused = os.environ.get("MINIMAGEN_SAMPLER_FUSED", "1") != "0"
     grouped = fused and 0 < lib.mi_sampler_group_size(n) <= group_max and not st.group_failed
-    kind = "small" if (fused and n <= 16384) else "group" if grouped else "separate"
+    clip = {'dynamic': None, 'static': 1, 'none': 0}[call.threshold]
+    kind = "direct" if clip is not None else "small" if (fused and n <= 16384) else "group" if grouped else "separate"
     group = kind == "group"
     if st.group_heal:
         st.group_sync.zero_()               # stream-ordered behind every launch queued on this lane: ticket, counters, histograms, error word
@@ -359,7 +366,7 @@ def p_sample_loop(im, unet, shape, ws, call: StageCall, run=None, *, noise_sched
     entries = {}
     for length, key in keys.items():
         entries[length] = _loop_entry(im, unet, st, ws, key, length, B=B, n=n, T=T, two=two, combine=combine, cond_scale=cond_scale, rescale=rescale, sched=sched,
-                                      kind=kind, group=group, k_lo=k_lo, k_hi=k_hi, w=w, noise_dev=noise_dev, seed=seed, sample0=sample0, stage=stage, use_graph=use_graph)
+                                      kind=kind, clip=clip, group=group, k_lo=k_lo, k_hi=k_hi, w=w, noise_dev=noise_dev, seed=seed, sample0=sample0, stage=stage, use_graph=use_graph)
     if use_graph:
         try:
             for length in lengths:
@@ -382,7 +389,7 @@ def p_sample_loop(im, unet, shape, ws, call: StageCall, run=None, *, noise_sched
     return img
 
 
-def _loop_entry(im, unet, st, ws, gkey, per, *, B, n, T, two, combine, cond_scale, rescale, sched, kind, group, k_lo, k_hi, w, noise_dev, seed,
+def _loop_entry(im, unet, st, ws, gkey, per, *, B, n, T, two, combine, cond_scale, rescale, sched, kind, clip, group, k_lo, k_hi, w, noise_dev, seed,
                 sample0, stage, use_graph):
     """The cached (or, for injected noise and eager runs, one-off) entry of ``per`` steps of p_sample_loop: dict(step, graph, per)."""
     lib, stream, eng = L.lib(), L.current_stream(), unet.engine()
@@ -396,7 +403,7 @@ def _loop_entry(im, unet, st, ws, gkey, per, *, B, n, T, two, combine, cond_scal
         if group and st.group_err_host is None:
             st.group_sync = torch.zeros(lib.mi_sampler_group_sync_bytes(B, n), dtype=torch.uint8, device=ws.dev)   # this workspace's launches only
             st.group_err_host = torch.zeros(1, dtype=torch.int32).pin_memory() if L.backend() == "hip-gfx950" else torch.zeros(1, dtype=torch.int32)
-        launch, advance = tail_launcher(st, ws, kind, cp, qp, pp, stream)
+        launch, advance = tail_launcher(st, ws, kind, cp, qp, pp, stream, clip)
         rp, sps = None, {}
         if rescale and st.rescale_partials is None:
             st.rescale_partials = torch.zeros(B, lib.mi_cfg_rescale_chunks(n), 4, dtype=torch.float64, device=ws.dev)
