@@ -663,7 +663,12 @@ int mi_chan_stats_fwd(const float* x, double* stats, int rows, int HW, void* str
  * layers.py:137):  y = (x - mean) rstd gamma + beta (beta may be NULL), biased variance, dim <= 1024; stat [rows][2] = (mean, rstd) is what the
  * backward reads (may be NULL when no backward follows).
  * Backward: dx = rstd (g - mean(g) - xh mean(g xh)) with g = dy gamma, xh = (x - mean) rstd; dgamma = sum_rows dy xh, dbeta = sum_rows dy through
- * `partial` ([mi_layernorm_bwd_nwg(rows, dim)][2][dim] floats), added in workgroup order by a second launch: deterministic.  dgamma == NULL: dx only. */
+ * `partial` ([mi_layernorm_bwd_nwg(rows, dim)][2][dim] floats), added in workgroup order by a second launch: deterministic.  dgamma == NULL: dx only
+ * (partial is not touched); dbeta may be NULL on its own.  mi_layernorm_bwd_nwg = min(512, ceil(rows / per_wg)) with per_wg = 256 rows at dim 8 / 16 /
+ * 32 (a work-item per row) and 4 otherwise (a wave per row); beyond 512 workgroups each walks ceil(rows / (512 per_wg)) groups of rows, and a
+ * workgroup left without rows writes zeros.
+ * Alignment: at dim 8 / 16 / 32, x, y, dy and dx are read and written 16 bytes at a time and must be 16-byte aligned; stat is accessed as
+ * (mean, rstd) pairs and must be 8-byte aligned at every dim (MI_ERR_INVALID otherwise).  Other dims: any float pointer. */
 int mi_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* stat, int rows, int dim, float eps, void* stream);
 int mi_layernorm_bwd_nwg(int rows, int dim);
 int mi_layernorm_bwd(const float* dy, const float* x, const float* gamma, const float* stat, float* dx, float* partial, float* dgamma, float* dbeta,
@@ -700,7 +705,20 @@ int mi_crossembed_wgrad(const mi_crossembed_wgrad_params* p, void* stream);
 /* the core of the folded cross-attention of the training graph (layers.py:220-251 with keys / values mapped into the token's channel space):
  *   out[b][i][:] = sum_h sum_j softmax_j(q[b][i] . kf[b][h][j]) vf[b][h][j]        (mask[b][j] == 0: row j takes no part)
  * forward (saves the per-(token, head) logsumexp) and backward (dq, and per-token-chunk partials of dkf / dvf that the caller adds) without the
- * [tokens x heads x context] score tensor.  fp32 VALU kernels; C in {8, 16, 32}, J * C <= 6144. */
+ * [tokens x heads x context] score tensor.  C in {8, 16, 32}, J * C <= 6144 and J <= 1024 (else MI_ERR_UNSUPPORTED); fp32 throughout, exp through
+ * the hardware exp2 on log2(e)-scaled scores; the backward recomputes the probabilities from lse.
+ *   C = 8 / 32 (and C = 16 with J > 384, or with MI_FOLDED_ATTN_VALU set: an A/B knob read per call): fp32 VALU kernels, a work-item per token
+ *     (forward, dq; 256 per workgroup) or per context row (dkf / dvf; 64 ceil(J / 64) per workgroup).
+ *   C = 16, J <= 384: v_mfma_f32_16x16x4_f32 kernels (exact fp32 products).  Forward and dq pick <token tiles per wave, waves> by
+ *     wg256 = ceil(n / 256) * B:  <1,4> below 256,  <2,4> for 256 .. 511,  <2,8> from 512; each with LDS for 17 context tiles of 16 rows (J <= 272)
+ *     or 24.  dq takes this form only with oh != NULL; without it the VALU dq kernel recomputes D = sum_j p_j dP_j / sum_j p_j (one more pass over the
+ *     context; same results within rounding).
+ *     dkf / dvf: <context tiles, waves> = <12,4> (J <= 192), <18,6> (J <= 288), <24,8>; a workgroup per (token chunk, head, image), the chunks
+ *     being ceil(n / nchunk) tokens each -- trailing chunks may be ragged or empty and still write their (zero) partials.
+ * Domain: every image needs at least ONE live context row (mask[b][j] != 0 for some j), otherwise its outputs are NaN (0 / 0 in the softmax); the
+ * layer always has its null row.  Rows the mask removes get exact zeros in dkf / dvf.
+ * Alignment: at C = 16, q, kf, vf, dout, out, oh, dq, dkf and dvf are read and written 16 bytes at a time and must be 16-byte aligned
+ * (MI_ERR_INVALID otherwise; every row is 64 bytes, so an aligned base suffices).  C = 8 / 32: any float pointer. */
 typedef struct mi_folded_attn_params {
     int B, n, H, J, C, nchunk;
     const float* q;                 /* [B][n][C] */

@@ -106,11 +106,16 @@ __global__ __launch_bounds__(256) void folded_attn_dq_kernel(mi_folded_attn_para
         if (p.oh) {                                        // D = sum_j p_j dP_j = dO . (sum_j p_j vf_j) = dO . O_h
             D = dotc<CC>(g, p.oh + (row * p.H + h) * CC);
         } else {
+            // over the sum of the recomputed probabilities: their common factor 1 + e (the roundings of lse, |e| ~ ulp(lse)) then cancels in D as it
+            // does in dO . O_h -- left in, dS = p (dP - D) is off by e D p in absolute terms, far above a dq that a peaked softmax makes small
+            float ps = 0.f;
             for (int j = 0; j < p.J; ++j) {
                 if (live[j] == 0.f) continue;
                 const float pj = __builtin_amdgcn_exp2f(dotc<CC>(q, ks + j * CC) - lse);
                 D = fmaf(pj, dotc<CC>(g, vs + j * CC), D);
+                ps += pj;
             }
+            D /= ps;
         }
         for (int j = 0; j < p.J; ++j) {
             if (live[j] == 0.f) continue;
@@ -511,6 +516,12 @@ int folded_dispatch(const mi_folded_attn_params* q, int which, void* stream) {
     if (q->J > AT_JMAX || q->J * q->C > AT_CAP) { mi_set_error("mi_folded_attn: context of %d rows x %d channels does not fit (J * C <= %d)", q->J, q->C, AT_CAP); return MI_ERR_UNSUPPORTED; }
     if (which == 0 && !q->out) { mi_set_error("mi_folded_attn_fwd: out missing"); return MI_ERR_INVALID; }
     if (which >= 1 && (!q->dout || !q->dsum)) { mi_set_error("mi_folded_attn_bwd: dout / dsum missing"); return MI_ERR_INVALID; }
+    if (q->C == 16) {                                                  // the matrix-core forms read and write 16 bytes at a time (NULL passes: checked above where required)
+        const size_t bits = reinterpret_cast<size_t>(q->q) | reinterpret_cast<size_t>(q->kf) | reinterpret_cast<size_t>(q->vf) | reinterpret_cast<size_t>(q->oh) |
+                            (which == 0 ? reinterpret_cast<size_t>(q->out)
+                                        : reinterpret_cast<size_t>(q->dout) | reinterpret_cast<size_t>(q->dq) | reinterpret_cast<size_t>(q->dkf) | reinterpret_cast<size_t>(q->dvf));
+        if (bits & 15) { mi_set_error("mi_folded_attn: at C = 16, q / kf / vf / out / oh / dout / dq / dkf / dvf must be 16-byte aligned"); return MI_ERR_INVALID; }
+    }
     hipStream_t st = (hipStream_t)stream;
     const bool valu_fwd = getenv("MI_FOLDED_ATTN_VALU") != nullptr;    // (read per call: the GPU test flips it in-process)          // A/B knob: the fp32 VALU kernels at C = 16 too
     if (which == 0 && q->C == 16 && q->J <= 16 * 24 && !valu_fwd) {

@@ -11,6 +11,14 @@ namespace {
 
 constexpr int LN_NT = 256, LN_MAXD = 1024;
 
+// sum of a[0 .. N) as a balanced tree: log2 N roundings on the way of every element instead of up to N - 1 -- and a row of equal values sums
+// exactly, so that its mean is the value itself and rstd = 1 / sqrt(eps) ~ 316 has no rounding error of the mean to amplify
+template <int N>
+__device__ __forceinline__ float ln_tree_sum(const float* a) {
+    if constexpr (N == 1) return a[0];
+    else return ln_tree_sum<N / 2>(a) + ln_tree_sum<N / 2>(a + N / 2);
+}
+
 // ---- a work-item per row (dim <= 32, dim % 4 == 0)
 template <int D>
 __global__ __launch_bounds__(LN_NT) void ln_fwd_rows_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -20,10 +28,7 @@ __global__ __launch_bounds__(LN_NT) void ln_fwd_rows_kernel(const float* __restr
     float v[D];
 #pragma unroll
     for (int c = 0; c < D; c += 4) { const float4 t = *reinterpret_cast<const float4*>(x + (size_t)row * D + c); v[c] = t.x; v[c + 1] = t.y; v[c + 2] = t.z; v[c + 3] = t.w; }
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < D; ++c) s += v[c];
-    const float mean = s / (float)D;
+    const float mean = ln_tree_sum<D>(v) / (float)D;
     float q = 0.f;
 #pragma unroll
     for (int c = 0; c < D; ++c) { const float d = v[c] - mean; q = fmaf(d, d, q); }
@@ -187,10 +192,17 @@ __global__ __launch_bounds__(LN_NT) void ln_bwd_reduce_kernel(const float* __res
 
 bool ln_rows_form(int dim) { return dim == 8 || dim == 16 || dim == 32; }
 
+// the work-item-per-row kernels read and write rows 16 bytes at a time; (mean, rstd) travels as one 8-byte pair in either form
+bool ln_misaligned(int dim, const void* a, const void* b, const void* c, const void* stat) {
+    const size_t rows16 = reinterpret_cast<size_t>(a) | reinterpret_cast<size_t>(b) | reinterpret_cast<size_t>(c);
+    return (ln_rows_form(dim) && (rows16 & 15)) || (reinterpret_cast<size_t>(stat) & 7);
+}
+
 }  // namespace
 
 extern "C" int mi_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* stat, int rows, int dim, float eps, void* stream) {
     if (rows <= 0 || dim <= 0 || dim > LN_MAXD || !x || !gamma || !y) { mi_set_error("mi_layernorm_fwd: need rows > 0, 0 < dim <= %d (got %d, %d)", LN_MAXD, rows, dim); return MI_ERR_INVALID; }
+    if (ln_misaligned(dim, x, y, nullptr, stat)) { mi_set_error("mi_layernorm_fwd: at dim 8 / 16 / 32, x and y must be 16-byte aligned; stat 8-byte aligned"); return MI_ERR_INVALID; }
     hipStream_t st = (hipStream_t)stream;
     float2* s2 = reinterpret_cast<float2*>(stat);
     const dim3 g((rows + LN_NT - 1) / LN_NT);
@@ -213,6 +225,7 @@ extern "C" int mi_layernorm_bwd(const float* dy, const float* x, const float* ga
                                 int rows, int dim, void* stream) {
     const int nwg = mi_layernorm_bwd_nwg(rows, dim);
     if (nwg == 0 || !dy || !x || !gamma || !stat || !dx || (dgamma && !partial)) { mi_set_error("mi_layernorm_bwd: bad arguments (rows %d, dim %d)", rows, dim); return MI_ERR_INVALID; }
+    if (ln_misaligned(dim, dy, x, dx, stat)) { mi_set_error("mi_layernorm_bwd: at dim 8 / 16 / 32, dy, x and dx must be 16-byte aligned; stat 8-byte aligned"); return MI_ERR_INVALID; }
     hipStream_t st = (hipStream_t)stream;
     const float2* s2 = reinterpret_cast<const float2*>(stat);
     float* part = dgamma ? partial : nullptr;

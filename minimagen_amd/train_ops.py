@@ -557,6 +557,13 @@ def crossembed_forward(layer, x: torch.Tensor, lowres) -> torch.Tensor:
     return _CrossEmbedFn.apply(x, lowres, tabs, cv[0].weight, cv[0].bias, cv[1].weight, cv[1].bias, cv[2].weight, cv[2].bias)
 
 
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """a contiguous tensor whose first element is 16-byte aligned: ``t`` itself, or a copy when it is a view that starts in the middle of a line
+    (the C = 16 attention kernels and the dim 8 / 16 / 32 LayerNorm kernels move 16 bytes at a time and refuse other pointers)"""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def folded_attention_supported(q: torch.Tensor, kf: torch.Tensor) -> bool:
     """mi_folded_attn_fwd / _bwd: fp32, C in {8, 16, 32}, J * C <= 6144 (the BASELINE U-Nets: C = 16, J = 259 / 261)"""
     return (ENABLED and q.dtype == torch.float32 and (q.is_cuda or FORCE) and q.shape[-1] in (8, 16, 32) and kf.shape[2] * kf.shape[3] <= 6144
@@ -571,7 +578,7 @@ class _FoldedAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, kf, vf, mask):
         lib = L.lib()
-        q, kf, vf = q.contiguous(), kf.contiguous(), vf.contiguous()
+        q, kf, vf = _aligned16(q), _aligned16(kf), _aligned16(vf)
         L.require_device(q, kf, vf)
         B, n, Cc = q.shape
         H, J = kf.shape[1], kf.shape[2]
@@ -590,7 +597,7 @@ class _FoldedAttnFn(torch.autograd.Function):
     def backward(ctx, dout):
         lib = L.lib()
         q, kf, vf, m8, lse, oh = ctx.saved_tensors
-        dout = dout.contiguous()
+        dout = _aligned16(dout)
         B, n, Cc = q.shape
         H, J = kf.shape[1], kf.shape[2]
         nchunk = max(1, min(n // 128, -(-2048 // (B * H))))
@@ -685,7 +692,7 @@ class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps):
         lib = L.lib()
-        x2 = x.contiguous().view(-1, x.shape[-1])
+        x2 = _aligned16(x).view(-1, x.shape[-1])
         L.require_device(x2)
         rows, dim = x2.shape
         y = torch.empty_like(x2)
@@ -702,7 +709,7 @@ class _LayerNormFn(torch.autograd.Function):
         lib = L.lib()
         x2, w, stat = ctx.saved_tensors
         rows, dim = x2.shape
-        dy2 = dy.contiguous().view(rows, dim)
+        dy2 = _aligned16(dy).view(rows, dim)
         dx = torch.empty_like(x2)
         need_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
         partial = dgamma = dbeta = None
